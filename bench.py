@@ -40,6 +40,7 @@ TRANS_LANES_PER_CLK = 8        # v_exp_f32 / v_log_f32: 8 cycles per wave64 inst
 CLOCK_GHZ = 2.4
 N_REGIONS = 5                  # timed regions per headline figure: value = the first, value_spread = min / median / max of all
 PREWARM = 200                  # untimed launches before the first warmup / timed region (~14 ms)
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: budget of all written arrays together
 
 
 def parse_args(argv=None):
@@ -67,7 +68,37 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget (0 = skip)")
     ap.add_argument("--no-secondary", "--no-align", action="store_true", dest="no_secondary",
                     help="headline only: skip the secondary single-GPU measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, dest="dump_outputs",
+                    help="after the timed steps, write what the timed path computed in its last step (rank 0) as DIR/<name>.npy, float32; "
+                         f"at most {DUMP_MAX_BYTES >> 20} MB in all (a larger output is cut to a fixed, seeded sample of its elements)")
     return ap.parse_args(argv)
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor} as out_dir/<name>.npy (float32, float64 kept) and return what was written, for the JSON line.  The arrays
+    share DUMP_MAX_BYTES smallest first, each kept whole while it fits its equal share of what is left; one that does not is cut to
+    that share: flattened, at the sorted positions numpy.random.default_rng(0).choice(n, k, replace=False) -- the same positions in
+    every run with the same arguments."""
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().contiguous().cpu()
+        host[name] = a.double().numpy() if a.dtype.is_floating_point and a.element_size() == 8 else a.float().numpy()
+    budget = DUMP_MAX_BYTES - 256 * len(host)                 # (room for the .npy headers)
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for i, name in enumerate(sorted(host, key=lambda k: host[k].nbytes)):
+        a = host[name]
+        entry = {"shape": list(a.shape), "dtype": str(a.dtype)}
+        cap = budget // (len(host) - i)
+        if a.nbytes > cap:
+            k = cap // a.itemsize
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))]
+            entry["sampled_elements"] = int(k)
+        budget -= a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = entry
+    return {"dir": os.path.abspath(out_dir), "arrays": {k: written[k] for k in host}}
 
 
 def _free_port():
@@ -293,8 +324,12 @@ def run(args):
     if args.workload == "train_step":
         from vlgae_amd.bench import sharded_step as bench_train
         res = bench_train.measure(args, rank, world, dev, dry, barrier)
+        outputs = res.pop("outputs", None)
         if rank == 0:
-            print(json.dumps(bench_train.json_line(args, world, res, dry, share)), flush=True)
+            line = bench_train.json_line(args, world, res, dry, share)
+            if outputs is not None:
+                line["dump_outputs"] = dump_outputs(args.dump_outputs, outputs)
+            print(json.dumps(line), flush=True)
         if world > 1:
             dist.barrier()
             dist.destroy_process_group()
@@ -385,6 +420,12 @@ def run(args):
         spread_s = [elapsed] + [timed_region(None)[0] for _ in range(N_REGIONS - 1)]
         elapsed_small = None
 
+    # ---- --dump-outputs: what the last timed launch wrote (logZ and the expected counts), before any later measurement runs ----
+    dumped = None
+    if args.dump_outputs and rank == 0 and not dry:
+        sync()
+        dumped = dump_outputs(args.dump_outputs, {"logZ": h.logZ, "grad_dec": h.gdec, "grad_attach": h.gatt})
+
     # ---- multi-GPU: the sharded training step (configs[4]) beside the DP line, on every rank ----
     train_sharded = None
     if world > 1 and not args.no_secondary:
@@ -392,6 +433,7 @@ def run(args):
         import copy
         targs = copy.copy(args)
         targs.steps, targs.warmup = min(args.steps, 50), min(args.warmup, 10)
+        targs.dump_outputs = None
         try:
             train_sharded = bench_train.measure(targs, rank, world, dev, dry, barrier)
             train_sharded.update(steps=targs.steps, warmup=targs.warmup,
@@ -430,6 +472,8 @@ def run(args):
                    "parallelism": (f"dp{world}" if world > 1 else "single") + (" (DEBUG: ranks share one GPU, gloo)" if share else ""),
                    "allreduce_floats": (comm["allreduce_bytes"] // 4 if world > 1 else 0)},
     }
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if train_sharded is not None:
         out["train_step_sharded"] = train_sharded
     if world > 1:

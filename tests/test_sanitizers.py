@@ -41,14 +41,29 @@ def _build(kind, name, compiler, sources, extra=()):
     return out
 
 
+def _no_aslr():
+    """preexec_fn of the TSan child: address-space randomisation off for that process (personality ADDR_NO_RANDOMIZE, inherited
+    across exec).  gcc's TSan runtime only accepts a PIE executable mapped near 0x55.. ; where the kernel randomises mmap with
+    32 bits it can land above that range and the runtime stops with 'FATAL: ThreadSanitizer: unexpected memory mapping'.  If the
+    call is refused the child runs as before."""
+    import ctypes
+    libc = ctypes.CDLL(None, use_errno=True)
+    cur = libc.personality(0xFFFFFFFF)
+    if cur != -1:
+        libc.personality(cur | 0x0040000)
+
+
 def _child(kind, env_lib, tests, k=None, timeout=900):
-    env = dict(os.environ, LD_PRELOAD=_runtime(SAN[kind][1]), OMP_NUM_THREADS="4", **env_lib,
+    # the sanitizer runtime goes first in the preload list (ASan requires it); what the environment already preloads stays
+    preload = ":".join(p for p in (_runtime(SAN[kind][1]), os.environ.get("LD_PRELOAD")) if p)
+    env = dict(os.environ, LD_PRELOAD=preload, OMP_NUM_THREADS="4", **env_lib,
                ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1",
                TSAN_OPTIONS="halt_on_error=0:report_signal_unsafe=0:second_deadlock_stack=1")
     cmd = [sys.executable, "-m", "pytest", "-q", "-x", "-m", "not gpu", "-p", "no:cacheprovider", *tests]
     if k:
         cmd += ["-k", k]
-    proc = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=timeout)
+    proc = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=timeout,
+                          preexec_fn=_no_aslr if kind == "tsan" else None)
     tail = proc.stdout[-4000:]
     assert proc.returncode == 0, tail
     assert " passed" in proc.stdout and not any(r in proc.stdout for r in REPORTS), tail

@@ -135,6 +135,7 @@ def _measure(args, rank, world, dev, dry, barrier):
     sync = (lambda: None) if dry else (lambda: torch.cuda.synchronize(dev))
     pending = [0] * len(groups)
     state = {"comm": False}
+    keep_last = bool(getattr(args, "dump_outputs", None)) and not dry   # bench.py --dump-outputs: the last step's loss and gradients
 
     def on_grad(name, g):                                  # inside the backward pass: the gradient of `name` is final
         views[name].copy_(g.reshape(-1))                   # cast to fp32 in the copy
@@ -152,8 +153,10 @@ def _measure(args, rank, world, dev, dry, barrier):
             pending[gi] = len(gp)
         if comm:
             red.wait()                                     # synchronous SGD: last step's reduced gradient before this step's first kernel
-        step(None)
+        last = step(None)
         assert not any(pending), pending                   # every parameter's gradient arrived through its hook
+        if keep_last:
+            state["last"] = last
 
     # step_mode "graph" (default on a GPU): forward + backward + the packing of every gradient into the flat buffer are captured ONCE as a
     # HIP graph; a step is one replay, and the buckets' collectives are enqueued behind it.  Eager, the step is host-bound (~2.6 ms of
@@ -180,8 +183,11 @@ def _measure(args, rank, world, dev, dry, barrier):
             pending[gi] = len(gp)
         try:
             graph = torch.cuda.CUDAGraph()
+            state.pop("last", None)
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                step(None)
+                last = step(None)                          # (its tensors are the graph's outputs: every replay rewrites them)
+                if keep_last:
+                    state["last"] = last
                 red.flat[check:check + 1].fill_(words_local)   # (the averaged slot of the previous step is overwritten every replay)
             assert not any(pending), pending
         except Exception as e:                                 # noqa: BLE001 -- any capture failure takes the same exit
@@ -264,6 +270,10 @@ def _measure(args, rank, world, dev, dry, barrier):
                real_gradient_floats=n_real, allreduce_floats=n_model if world > 1 else 0)
     if "capture_error" in state:
         res["capture_error"] = state["capture_error"]          # graph mode was asked for and fell back to eager
+    if keep_last:
+        sync()
+        loss, grads, _ = state["last"]
+        res["outputs"] = dict(loss=loss, **{"grad." + k: grads[k] for k in sorted(grads)})
     return res
 
 

@@ -29,7 +29,17 @@ UNITS = DP_INST + (("vlg_dp.hip", "vlg_dp", DP_FLAGS), ("vlg_dp_pair.hip", "vlg_
     (src, os.path.splitext(src)[0], ()) for src in
     ("vlg_align.hip", "vlg_attn.hip", "vlg_ground.hip", "vlg_decode.hip", "vlg_arc.hip", "vlg_rel.hip", "vlg_gemm.hip", "vlg_langfeat.hip", "vlg_ff.hip", "vlg_ffgemm.hip", "vlg_encoders.hip", "vlg_scorer.hip", "vlg_feed.cpp", "vlg_capi.cpp"))
 SOURCES = tuple(sorted({u[0] for u in UNITS}))
-JOBS = max(1, min(len(UNITS), int(os.environ.get("VLGAE_BUILD_JOBS", os.cpu_count() or 4))))
+
+
+def _jobs():
+    """Parallel hipcc processes: VLGAE_BUILD_JOBS, else the usual job-count variables, else the CPUs this process may run on."""
+    for k in ("VLGAE_BUILD_JOBS", "MAX_JOBS", "CMAKE_BUILD_PARALLEL_LEVEL"):
+        if os.environ.get(k, "").strip().isdigit():
+            return int(os.environ[k])
+    return len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 4)
+
+
+JOBS = max(1, min(len(UNITS), _jobs()))
 
 
 def _hipcc():
