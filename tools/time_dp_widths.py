@@ -1,0 +1,121 @@
+#!/usr/bin/env python3
+"""Per-width timeline of the headline DMV1o launch (fused inside + outside, short image, B = 256, L = 40, bf16).
+
+Builds the stamped library variant (tools/build_variant.sh NAME -DVLG_STAMP=2: per-width stamps only, see DevX::wstamp) unless
+--lib names one, runs the headline launch a few times, and prints for every width of each pass, as the median over the first
+16 sentences (workgroups) of the last launch, in s_memtime cycles:
+  G, T          lanes per span and split points per lane (the schedule of vlg_dp_core.h: make_sched / group_log2)
+  live          wavefronts per direction that hold a span of that width (the others skip the body: kSkipDeadWaves)
+  body_max      slowest wavefront: previous barrier's release -> its body's end
+  body_min      fastest wavefront (a dead one when live < 4)
+  skew          last body end - first body end
+  bar           barrier: last body end -> release
+  width         release -> release
+and each wavefront's SIMD (HW_ID bits 5:4).  Usage:  python tools/time_dp_widths.py [--lib PATH] [--name stamp] [-D...]
+Extra -D arguments go to the variant build (e.g. -DVLG_MIRROR_RIGHT=0 for the unmirrored placement)."""
+import argparse
+import ctypes
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+KW, KBLOCKS = 64, 16
+KWORDS = 2 * KW * 2 * 8 + 8
+M32 = 1 << 32   # the stamps are the low 32 bits of s_memtime
+
+
+def group_log2(spans, w, cap):
+    lg = 0
+    while lg < 6 and (1 << lg) < w and spans * (2 << lg) <= cap:
+        lg += 1
+    return lg
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--lib", default=None, help="an already-built stamped variant")
+    ap.add_argument("--name", default="stamp")
+    ap.add_argument("--launches", type=int, default=20)
+    args, defs = ap.parse_known_args()
+    lib_path = args.lib
+    if lib_path is None:
+        out = subprocess.run(["bash", os.path.join(ROOT, "tools", "build_variant.sh"), args.name, "-DVLG_STAMP=2", *defs],
+                             check=True, capture_output=True, text=True, cwd=ROOT).stdout.split()
+        lib_path = os.path.join(ROOT, out[-1])
+    lib_path = os.path.abspath(lib_path)
+    os.environ["VLGAE_AMD_LIB"] = lib_path
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    from vlgae_amd import _C
+    import vlgae_amd.torch_struct as ts
+    from bench import synth
+
+    B, L = 256, 40
+    N = L + 1
+    dev = torch.device("cuda:0")
+    lib = _C.lib()
+    dec, attach, root = synth(B, L, 1000, dev, torch.float32)
+    md, ma = (t.to(torch.bfloat16).contiguous() for t in ts.DMV1o.merge(dec, attach, root))
+    lengths = torch.full((B,), L, dtype=torch.long, device=dev)
+    logZ = torch.empty(B, dtype=torch.float32, device=dev)
+    gdec = torch.zeros((B, N, 2, 2, 2), dtype=torch.float32, device=dev)
+    gatt = torch.zeros((B, N, N, 2), dtype=torch.float32, device=dev)
+    ws_bytes = lib.vlg_workspace_bytes(_C.OP_DMV1O_INSIDE_OUTSIDE, B, N, 0)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    sp = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    p = [_C.ptr(x) for x in (md, ma, lengths, logZ, gdec, gatt, ws)]
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    times = []
+    for _ in range(args.launches):
+        ev0.record()
+        _C.check(lib.vlg_dmv1o_inside_outside(p[0], p[1], p[2], B, N, _C.BF16, 0, None, p[3], p[4], p[5], p[6], ws_bytes, sp),
+                 "dmv1o_inside_outside")
+        ev1.record()
+        torch.cuda.synchronize()
+        times.append(ev0.elapsed_time(ev1) * 1e3)
+    handle = ctypes.CDLL(lib_path)
+    if not hasattr(handle, "vlg_dp_stamps"):   # an unstamped library: the launches alone (e.g. under a counter pass)
+        print(f"# {os.path.basename(lib_path)}: launch {np.median(times):.1f} us (median of {len(times)}); no stamps in this build")
+        return
+    buf = (ctypes.c_uint * (KBLOCKS * KWORDS))()
+    fn = handle.vlg_dp_stamps
+    fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t]
+    if fn(buf, KBLOCKS * KWORDS) != KWORDS:
+        raise SystemExit("vlg_dp_stamps failed")
+    a = np.frombuffer(buf, dtype=np.uint32).reshape(KBLOCKS, KWORDS).astype(np.int64)
+    st = a[:, :-8].reshape(KBLOCKS, 2, KW, 2, 8)   # [block][pass][w][body end | release][wave]
+    hw = a[:, -8:]
+    simd = (hw >> 4) & 3
+    print(f"# {os.path.basename(lib_path)}: B={B} L={L} bf16, launch {np.median(times):.1f} us (median of {len(times)}, stamped build)")
+    print(f"# SIMD of waves 0-7, first 4 workgroups: {[list(map(int, s)) for s in simd[:4]]}")
+    Ne = N
+    for pas, name in ((0, "inside"), (1, "outside")):
+        ws_ = list(range(1, Ne)) if pas == 0 else list(range(Ne - 1, 0, -1))
+        print(f"## {name} pass (cycles; median over {KBLOCKS} workgroups)")
+        print(f"{'w':>3} {'G':>3} {'T':>2} {'live':>4} {'body_max':>8} {'body_min':>8} {'skew':>6} {'bar':>6} {'width':>6}")
+        tot = {"width": 0, "body_max": 0, "bar": 0, "skew": 0}
+        for w in ws_:
+            prev = w - 1 if pas == 0 else w + 1
+            rel_prev = st[:, pas, prev, 1, :].max(axis=1)   # (prev = 0 / Ne: the pass-start stamp)
+            end = st[:, pas, w, 0, :]
+            rel = st[:, pas, w, 1, :].max(axis=1)
+            body = (end - rel_prev[:, None]) % M32
+            cap = 256
+            lg = group_log2(Ne - w, w, cap)
+            G = 1 << lg
+            T = (w + G - 1) >> lg
+            live = min(4, -(-((Ne - w) * G) // 64))
+            row = {"body_max": np.median(body.max(axis=1)), "body_min": np.median(body.min(axis=1)),
+                   "skew": np.median((end.max(axis=1) - end.min(axis=1)) % M32), "bar": np.median((rel - end.max(axis=1)) % M32),
+                   "width": np.median((rel - rel_prev) % M32)}
+            for k in tot:
+                tot[k] += row[k]
+            print(f"{w:>3} {G:>3} {T:>2} {live:>4} {row['body_max']:>8.0f} {row['body_min']:>8.0f} {row['skew']:>6.0f} "
+                  f"{row['bar']:>6.0f} {row['width']:>6.0f}")
+        print(f"sum  width {tot['width']:.0f}  body_max {tot['body_max']:.0f}  skew {tot['skew']:.0f}  barrier {tot['bar']:.0f}")
+
+
+if __name__ == "__main__":
+    main()

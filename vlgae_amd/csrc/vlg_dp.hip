@@ -185,6 +185,15 @@ static int run_dep(const void* arc, const int64_t* lengths, int B, int N, int in
 
 }  // namespace vlg
 
+#ifdef VLG_STAMP   // diagnostic build only (tools/time_dp_widths.py): not part of the C ABI
+extern "C" int vlg_dp_stamps(unsigned* dst, size_t words) {
+    const size_t n = sizeof(vlg::vlg_wstamp_dev) / sizeof(unsigned);
+    if (words < n) return -1;
+    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(vlg::vlg_wstamp_dev), n * sizeof(unsigned), 0, hipMemcpyDeviceToHost) == hipSuccess
+               ? (int)(n / vlg::kStampBlocks) : -2;
+}
+#endif
+
 // =====================================================================================================
 // C ABI (include/vlgae_amd.h)
 // =====================================================================================================

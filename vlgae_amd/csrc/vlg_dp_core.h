@@ -70,10 +70,15 @@ static inline float vlg_bits2f(uint32_t u) { float f; std::memcpy(&f, &u, 4); re
 #define VLG_SR_LOG 0
 #define VLG_SR_MAX 1
 #define VLG_LOWEST (-3.0e38f)
-#if defined(VLG_STAMP) && defined(__HIPCC__)
+#if defined(VLG_STAMP) && defined(__HIPCC__) && VLG_STAMP != 2
 #define VLG_STAMP_AT(x, k) (x).stamp(k)   // diagnostic build: cycle stamps between the segments of a phase
 #else
 #define VLG_STAMP_AT(x, k) ((void)0)
+#endif
+#if defined(VLG_STAMP) && defined(__HIPCC__)
+#define VLG_WSTAMP(x, pass, w, k) (x).wstamp((pass), (w), (k))   // diagnostic build: per-width body-end / barrier-release stamps
+#else                                                            // (VLG_STAMP=2: these alone, tools/time_dp_widths.py)
+#define VLG_WSTAMP(x, pass, w, k) ((void)0)
 #endif
 // Charts are kept in log2 units so that the hardware's native 2^x / log2 x need no scaling multiplies:
 // potentials are multiplied by log2(e) once at load, logZ by ln(2) once at store; the adjoint weights
@@ -174,6 +179,9 @@ VLG_HD int group_log2(int spans, int w, int nt, int budget) {
     while (lg < 6 && (1 << lg) < w && spans * (2 << lg) <= cap) ++lg;
     return lg;
 }
+#ifndef VLG_MIRROR_RIGHT
+#define VLG_MIRROR_RIGHT 1   // short image: the right direction's span slots dealt from its last wavefront down (dir_lane); 0 for A/B timing
+#endif
 #define VLG_GROUP_LOG2_FW(spans, w, nt) group_log2(spans, w, nt, VLG_DP_LANES_FW)
 #define VLG_GROUP_LOG2_BW(spans, w, nt) group_log2(spans, w, nt, 512)   // DepTree outside pass: whole workgroup per width
 
@@ -458,12 +466,25 @@ VLG_HD void dmv_fw_width(const DmvCtx& c, int w, int lgr, int t, int nd, X& x, i
     }
 }
 
+// A lane's index t within its direction's half of the workgroup (tid < nd: left, else right).  MIRROR (the short image): the right
+// half deals its span slots from its LAST wavefront down.  Waves k and k + 4 of a workgroup share a SIMD (HW_ID, read by
+// tools/time_dp_widths.py), and at the small widths only
+// the first wavefront(s) of a direction have live spans (kSkipDeadWaves), so with t = tid - nd both directions' chains ran on the same
+// SIMD(s) while the others idled; mirrored, the live wavefronts of the two directions sit on different SIMDs up to two per direction.
+// Whole wavefronts are permuted: a lane's position inside its wavefront, and so every lane group and butterfly, is unchanged.
+template <bool MIRROR>
+VLG_HD int dir_lane(int tid, int nd, bool right) {
+    if (!right) return tid;
+    const int t = tid - nd;
+    return MIRROR && (nd & 63) == 0 ? ((nd - 64 - (t & ~63)) | (t & 63)) : t;
+}
+
 // all widths of one segment (constant group size), one barrier per width
 template <int SR, bool BWD, int LG, int LONGSPAN, typename X>
 VLG_HD void dmv_fw_segment(const DmvCtx& c, int w0, int w1, int tid, int nt, X& x) {
     const int nd = nt >> 1;                 // lanes per direction
     const bool right = x.uniform(tid >= nd);   // wave-uniform on the device (nd is a multiple of 64)
-    const int t = right ? tid - nd : tid;
+    const int t = dir_lane<VLG_MIRROR_RIGHT && LONGSPAN == kSpansShort>(tid, nd, right);
     for (int w = w0; w < w1; ++w) {
 #ifndef VLG_ABL_NOBODY
 #ifdef VLG_DIR_RT_FW   // (measured: 33.4 -> 39.4 us for the inside pass -- its selects sit in the per-term loop; see dmv_bw_segment)
@@ -473,15 +494,18 @@ VLG_HD void dmv_fw_segment(const DmvCtx& c, int w0, int w1, int tid, int nt, X& 
         else dmv_fw_width<SR, BWD, 0, LG, LONGSPAN>(c, w, LG, t, nd, x);
 #endif
 #endif
+        VLG_WSTAMP(x, 0, w, 0);
 #ifndef VLG_ABL_NOBARRIER
         x.sync();
 #endif
+        VLG_WSTAMP(x, 0, w, 1);
     }
 }
 
 template <int SR, bool BWD, int LONGSPAN, typename X>
 VLG_HD void dmv_fw_all(const DmvCtx& c, int tid, int nt, X& x) {
     const Sched sc = make_sched(c.Ne, nt >> 1, VLG_DP_LANES_FW);
+    VLG_WSTAMP(x, 0, 0, 1);   // the pass starts: the "release" before width 1
     dmv_fw_segment<SR, BWD, 0, LONGSPAN>(c, sc.first[0], sc.first[1], tid, nt, x);
     dmv_fw_segment<SR, BWD, 1, LONGSPAN>(c, sc.first[1], sc.first[2], tid, nt, x);
     dmv_fw_segment<SR, BWD, 2, LONGSPAN>(c, sc.first[2], sc.first[3], tid, nt, x);
@@ -745,7 +769,7 @@ VLG_HD void dmv_bw_segment_p(const DmvCtx& c, int w0, int w1, int tid, int nt, X
     const int nd = nt >> 1;
     const bool right = x.uniform(tid >= nd);
     const int dir = right ? 1 : 0;
-    const int t = right ? tid - nd : tid;
+    const int t = dir_lane<VLG_MIRROR_RIGHT>(tid, nd, right);
     const int rr = t & (G - 1), slot = t >> LG, wslot = (t & ~63) >> LG;   // wslot: the first span of this lane's wavefront
     const int Ds = VLG_MUL24(slot, c.P + 1);
     BwVals<TM> va, vb;   // ping-pong: the body of one width reads one and fills the other (no copies)
@@ -765,7 +789,9 @@ VLG_HD void dmv_bw_segment_p(const DmvCtx& c, int w0, int w1, int tid, int nt, X
         } else if (TM == 1 || T == 1) dmv_bw_span_p<SR, -1, 1, TM, X, NC>(c, w, G, D, live, rr, x, cur, nxt, more, w - 1, Dn, dir);
         else if (TM == 2 || T == 2) dmv_bw_span_p<SR, -1, 2, TM, X, NC>(c, w, G, D, live, rr, x, cur, nxt, more, w - 1, Dn, dir);
         else dmv_bw_span_p<SR, -1, 3, TM, X, NC>(c, w, G, D, live, rr, x, cur, nxt, more, w - 1, Dn, dir);
+        VLG_WSTAMP(x, 1, w, 0);
         x.sync();
+        VLG_WSTAMP(x, 1, w, 1);
     };
     for (int w = w1 - 1; w >= w0; w -= 2) {
         one_width(w, va, vb);
@@ -969,6 +995,7 @@ VLG_HD void dmv_bw_all(const DmvCtx& c, int tid, int nt, X& x) {
     const Sched sc = make_sched(c.Ne, nt >> 1, VLG_DP_LANES_BW);
 #ifndef VLG_NO_BW_PREFETCH
     if constexpr (LONGSPAN == kSpansShort) {   // the short-sentence image: value reads one width ahead (dmv_bw_segment_p)
+        VLG_WSTAMP(x, 1, c.Ne, 1);   // the pass starts: the "release" before width Ne - 1
         dmv_bw_segment_p<SR, 6>(c, sc.first[6], sc.first[7], tid, nt, x);
         dmv_bw_segment_p<SR, 5>(c, sc.first[5], sc.first[6], tid, nt, x);
         dmv_bw_segment_p<SR, 4>(c, sc.first[4], sc.first[5], tid, nt, x);

@@ -18,6 +18,15 @@ namespace vlg {
 #endif
 constexpr int kThreads = VLG_DP_THREADS;    // lanes per sentence (workgroup size)
 constexpr size_t kLdsBudget = 160 * 1024;   // CDNA4 LDS per CU / per workgroup
+#ifdef VLG_STAMP
+// Diagnostic build (tools/time_dp_widths.py): the DMV1o kernels of the first kStampBlocks sentences copy their per-width stamp table
+// (DevX::wstamp) and each wavefront's HW_ID register to vlg_wstamp_dev; the host reads it with vlg_dp_stamps().
+constexpr int kStampW = 64;                                  // widths per pass (N <= kShortN in the short image)
+constexpr int kStampBlocks = 16;
+constexpr int kStampWaves = kThreads / 64;
+constexpr int kStampWords = 2 * kStampW * 2 * 8 + 8;         // [pass][w][body end | barrier release][wave], then HW_ID per wave
+static __device__ unsigned vlg_wstamp_dev[kStampBlocks][kStampWords];
+#endif
 
 // ---- cross-lane exchange: lane l <- lane l ^ K, for values that are uniform over aligned K-blocks ------
 // (true at every step of an ascending butterfly all-reduce).  K = 1, 2 are quad permutes; K = 4 / 8 use
@@ -160,6 +169,13 @@ struct DevX {
     __device__ __forceinline__ bool uniform(bool v) { return __builtin_amdgcn_readfirstlane((int)v) != 0; }
     __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 #ifdef VLG_STAMP
+    // per-width stamps (VLG_WSTAMP in the segment loops): wst = this workgroup's LDS table [pass][w][k][wave] of the low 32 bits of
+    // s_memtime, k = 0 when the wave has finished its body of width w, k = 1 when the barrier behind it has released the wave
+    unsigned* wst = nullptr;
+    __device__ __forceinline__ void wstamp(int pass, int w, int k) {
+        const unsigned t = (unsigned)__builtin_amdgcn_s_memtime();
+        if (wst && (threadIdx.x & 63) == 0) wst[((pass * kStampW + w) * 2 + k) * 8 + (threadIdx.x >> 6)] = t;
+    }
     unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, last = 0;
     __device__ __forceinline__ void stamp(int k) {   // acc[k & 7] += cycles since the previous stamp
         unsigned long long t;
@@ -284,7 +300,19 @@ __device__ __forceinline__ void dmv1o_sentence(int b, const typename In::T* __re
     io.gatt = (BWD && gatt) ? gatt + att_off : nullptr;
     io.heads = (BWD && heads) ? heads + (size_t)b * N : nullptr;
     DevX x;
+#ifdef VLG_STAMP
+    __shared__ unsigned wst[kStampWords];
+    for (int i = tid; i < kStampWords; i += kThreads) wst[i] = 0u;
+    __syncthreads();
+    if ((tid & 63) == 0) wst[kStampWords - 8 + (tid >> 6)] = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // hwreg(HW_REG_HW_ID): SIMD in bits 5:4
+    x.wst = wst;
+#endif
     dmv_run<SR, BWD, spans_of(MODE)>(c, io, (BWD && glogZ) ? glogZ[b] : 1.f, logZ + b, tid, kThreads, x);   // long-sentence placements: chunked long spans
+#ifdef VLG_STAMP
+    __syncthreads();
+    if (b < kStampBlocks)
+        for (int i = tid; i < kStampWords; i += kThreads) vlg_wstamp_dev[b][i] = wst[i];
+#endif
 }
 
 template <int SR, int MODE, bool BWD, typename In>
