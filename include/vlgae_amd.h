@@ -173,6 +173,30 @@ int vlg_grounding_loss(const void* txt, const void* vis, const uint8_t* tmask, c
                        const float* pen, const uint8_t* seg_of_v, int n_seg, int B, int Q, int V, int d, int in_dtype,
                        float neg_inf, float num_token, float w_vis2txt, void* ws, size_t ws_bytes, float* out_sums,
                        float* g_txt, float* g_vis, void* stream);
+/* The same with the normaliser read from DEVICE memory: num_token points to one fp32 value (e.g. what vlg_step_batch_prepare
+ * writes), read by the kernel that forms the sums, so that one captured HIP graph serves every batch of its shape.  Every other
+ * argument, every kernel and the workspace are vlg_grounding_loss's; num_token NULL is VLG_ERR_ARG. */
+int vlg_grounding_loss_ntok(const void* txt, const void* vis, const uint8_t* tmask, const uint8_t* vmask, const float* marginal,
+                            const float* pen, const uint8_t* seg_of_v, int n_seg, int B, int Q, int V, int d, int in_dtype,
+                            float neg_inf, const float* num_token, float w_vis2txt, void* ws, size_t ws_bytes, float* out_sums,
+                            float* g_txt, float* g_vis, void* stream);
+
+/* The per-batch data of one training step (vlgae_amd/train_step.py, batch_on_device=True) in ONE launch, written into caller-owned
+ * buffers -- what the step would otherwise derive on the host from the batch (src/model/joint.py:140-170, :446-470; src/utility/fn.py:50-56):
+ *   lengths [B] int64, tag [B,L] int64 (any ids), box_mask [B,R] uint8 (0 / non-zero); factor layout add_rel / add_attr / add_image
+ *   (obj | rel | attr | img, V = R + R^2 + R + 1 with all on); POS sets pos_obj[n_obj] / pos_rel[n_rel] / pos_attr[n_attr] int64
+ *   (device; a set of an absent factor is ignored);
+ *   vmask [B,V] uint8 = box | strict upper triangle of box x box | box | 1 (vis_feat_unprune's mask);
+ *   pen [B,Q,S] fp32 (NULL = no prior; S = number of factors, Q >= L + 1): rows q = 1..L hold prior_scale times the number of named
+ *     factors f != s whose POS set holds tag[b,q-1], the other rows 0 -- the table vlg_grounding_loss takes with seg_of_v;
+ *   num_token = sum_b lengths[b] (fp32); coef[2] = [alpha, -(1 - alpha)] / (num_token + 1e-12) (the coefficients rounded to fp32 from
+ *     double, IEEE division); seed_max [B] = coef[1].
+ * Equal bit for bit to the torch formulation (encoders.factor_mask, align.grounding_prior, the coefficients of train_step.build).
+ * One workgroup per sentence; every workgroup sums the lengths itself: no atomics, no workspace. */
+int vlg_step_batch_prepare(const int64_t* lengths, const int64_t* tag, const uint8_t* box_mask, int B, int L, int R, int Q, int add_rel,
+                           int add_attr, int add_image, const int64_t* pos_obj, int n_obj, const int64_t* pos_rel, int n_rel,
+                           const int64_t* pos_attr, int n_attr, float prior_scale, double alpha, uint8_t* vmask, float* pen,
+                           float* num_token, float* coef, float* seed_max, void* stream);
 
 /* gather_logit_reduced, src/model/joint.py:421-432 (the input of loss_grounding_cap_img_ll :493-499 and
  * decode_grounding_on_image :506-510), for B captions x B images without the [B,B,Q,V] tensor:
@@ -603,7 +627,7 @@ int vlg_selftest_xlane(int* scratch, void* stream);
 /* Thread-local message for the last non-zero return on this thread ("" if none). */
 const char* vlg_last_error(void);
 
-/* Library / ABI version, e.g. 142 = 0.1.4.2 (round 6, 142: vlg_attn_fuse / vlg_attn_fuse_backward take key_chunk and a workspace -- the key-split form for the
+/* Library / ABI version, e.g. 142 = 0.1.4.2 (145: vlg_step_batch_prepare and vlg_grounding_loss_ntok added; round 6, 142: vlg_attn_fuse / vlg_attn_fuse_backward take key_chunk and a workspace -- the key-split form for the
  * shipped 1369-key factor layout -- and the gradients' storage type; vlg_attn_fuse_workspace added; round 5, 141: vlg_dropout, vlg_rng_advance, vlg_vis_encoder(_backward) added, vlg_linear_wgrad takes ld_dw and in_dtype;
  * the Python binding refuses a library whose version differs from the one it was written against; round 4: vlg_langfeat_* take the activations' storage type and the SharedDropout masks,
  * vlg_langfeat_rowscale, vlg_ff_* added, vlg_ndmv_potentials* take row strides and the gradients' storage type; round 3, 120: vlg_linear_wgrad, vlg_langfeat_*, vlg_ndmv_potentials*, vlg_dmv1o_viterbi added;

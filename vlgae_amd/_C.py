@@ -62,6 +62,10 @@ SIGNATURES = {
     "vlg_grounding_loss_workspace": (_sz, [_i, _i, _i]),
     "vlg_grounding_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _sz, _vp, _vp,
                                 _vp, _vp]),
+    "vlg_grounding_loss_ntok": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _f, _vp, _sz, _vp, _vp,
+                                     _vp, _vp]),
+    "vlg_step_batch_prepare": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _f, ctypes.c_double, _vp, _vp,
+                                    _vp, _vp, _vp, _vp]),
     "vlg_align_reduced_workspace": (_sz, [_i, _i]),
     "vlg_align_reduced": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp, _vp]),
     "vlg_align_reduced_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
@@ -130,7 +134,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 144   # what include/vlgae_amd.h declares at this revision; lib() refuses any other library (argument lists differ between versions)
+ABI_VERSION = 145  # what include/vlgae_amd.h declares at this revision; lib() refuses any other library (argument lists differ between versions)
 
 
 def lib():

@@ -308,8 +308,7 @@ def grounding_prior(tag, factor_names, vis_split, pos_for, Q, scale=100.0):
     B, L = tag.shape
     S = len(vis_split)
     dev = tag.device
-    seg_of_v = torch.repeat_interleave(torch.arange(S, dtype=torch.uint8, device=dev),
-                                       torch.as_tensor(list(vis_split), device=dev))
+    seg_of_v = segment_map(vis_split, dev)
     pen = torch.zeros((B, Q, S), dtype=torch.float32, device=dev)
     for f, name in enumerate(factor_names):
         if name not in ("obj", "rel", "attr"):
@@ -318,6 +317,55 @@ def grounding_prior(tag, factor_names, vis_split, pos_for, Q, scale=100.0):
         others = [s for s in range(S) if s != f]
         pen[:, 1:L + 1, others] += hit.unsqueeze(-1)
     return pen, seg_of_v
+
+
+def segment_map(vis_split, device):
+    """seg_of_v [V] uint8 of grounding_prior: the factor segment of every region column -- a function of the layout alone."""
+    return torch.repeat_interleave(torch.arange(len(vis_split), dtype=torch.uint8, device=device),
+                                   torch.as_tensor(list(vis_split), device=device))
+
+
+def step_batch_prepare(lengths, tag, box_mask, factors, pos_for, Q, alpha, vmask, pen, num_token, coef, seed_max, scale=100.0):
+    """The per-batch data of a training step in ONE launch (vlg_step_batch_prepare), into the caller's buffers: vmask [B,V] bool / uint8
+    = encoders.factor_mask(box_mask, ...), pen [B,Q,S] float32 = grounding_prior(tag, ..., scale)[0] (or None: no prior), num_token (0-d
+    float32) = lengths.sum(), coef [2] = [alpha, -(1 - alpha)] / (num_token + 1e-12), seed_max [B] = coef[1] -- bit for bit what the
+    torch formulation gives, read from device memory only (capturable: a replay serves any batch of the shape).  lengths [B] / tag [B,L]
+    int64, box_mask [B,R] bool / uint8, factors among ("rel", "attr", "img"), pos_for = {"obj", "rel", "attr": int64 device tensors}."""
+    B, L = tag.shape
+    R = box_mask.shape[1]
+    dev = lengths.device
+    for name, t in (("lengths", lengths), ("tag", tag)):
+        if t.dtype != torch.int64 or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"step_batch_prepare: {name} must be contiguous int64 on {dev}, got {t.dtype} on {t.device}")
+    bm = _C.mask_u8(box_mask, dev)
+    if tuple(bm.shape) != (B, R) or tuple(lengths.shape) != (B,):
+        raise ValueError(f"step_batch_prepare: lengths {tuple(lengths.shape)} / box_mask {tuple(bm.shape)} do not match tag [B,L] = {(B, L)}")
+    V = R + ("rel" in factors) * R * R + ("attr" in factors) * R + ("img" in factors)
+    S = 1 + sum(f in factors for f in ("rel", "attr", "img"))
+    vm = vmask.view(torch.uint8) if vmask.dtype == torch.bool else vmask
+    for name, t, shape, dt in (("vmask", vm, (B, V), torch.uint8), ("num_token", num_token, (), torch.float32), ("coef", coef, (2,), torch.float32),
+                               ("seed_max", seed_max, (B,), torch.float32), ("pen", pen, (B, int(Q), S), torch.float32)):
+        if t is not None and (t.dtype != dt or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape)):
+            raise ValueError(f"step_batch_prepare: {name} must be contiguous {dt} {shape}, got {t.dtype} {tuple(t.shape)}")
+        if t is not None and t.device != dev:
+            raise ValueError(f"step_batch_prepare: {name} on {t.device}, lengths on {dev}")
+    ids = [pos_for.get(k) for k in ("obj", "rel", "attr")]
+    for t in ids:
+        if t is not None and (t.dtype != torch.int64 or not t.is_contiguous() or t.device != dev):
+            raise ValueError("step_batch_prepare: POS sets must be contiguous int64 device tensors")
+    _C.require_gpu(lengths, "step_batch_prepare")      # (after the argument checks: host tensors never reach the launch)
+    args = []
+    for t in ids:
+        args += [_C.ptr(t) if t is not None and t.numel() else None, 0 if t is None else t.numel()]
+    _C.check(_C.lib().vlg_step_batch_prepare(_C.ptr(lengths), _C.ptr(tag), _C.ptr(bm), B, L, R, int(Q), int("rel" in factors),
+                                             int("attr" in factors), int("img" in factors), *args, float(scale), float(alpha), _C.ptr(vm),
+                                             _C.ptr(pen), _C.ptr(num_token), _C.ptr(coef), _C.ptr(seed_max), _C.stream_of(lengths)),
+             "step_batch_prepare")
+
+
+def _device_num_token(t):
+    """A 0-d float32 GPU tensor: the normaliser is read from device memory (vlg_grounding_loss_ntok); anything else is a host number."""
+    return torch.is_tensor(t) and t.dim() == 0 and t.dtype == torch.float32 and t.is_cuda
 
 
 class _GroundingLoss(torch.autograd.Function):
@@ -342,10 +390,16 @@ class _GroundingLoss(torch.autograd.Function):
         need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         nbytes = _C.lib().vlg_grounding_loss_workspace(B, Q, V)
         (sums, g_txt, g_vis), ws = _C.alloc_f32(dev, ((3,), (B, Q, d) if need else None, (B, V, d) if need else None), nbytes)
-        _C.check(_C.lib().vlg_grounding_loss(_C.ptr(txt_c), _C.ptr(vis_c), _C.ptr(tm), _C.ptr(vm), _C.ptr(marg), _C.ptr(pen),
-                                             _C.ptr(seg_of_v), n_seg, B, Q, V, d, dt, float(neg_inf), float(num_token),
-                                             float(w_vis2txt), _C.ptr(ws), nbytes, _C.ptr(sums), _C.ptr(g_txt), _C.ptr(g_vis),
-                                             _C.stream_of(txt_c)), "grounding_loss")
+        if _device_num_token(num_token):   # the normaliser in device memory (a captured step serves every batch of its shape)
+            _C.check(_C.lib().vlg_grounding_loss_ntok(_C.ptr(txt_c), _C.ptr(vis_c), _C.ptr(tm), _C.ptr(vm), _C.ptr(marg), _C.ptr(pen),
+                                                      _C.ptr(seg_of_v), n_seg, B, Q, V, d, dt, float(neg_inf), _C.ptr(num_token),
+                                                      float(w_vis2txt), _C.ptr(ws), nbytes, _C.ptr(sums), _C.ptr(g_txt), _C.ptr(g_vis),
+                                                      _C.stream_of(txt_c)), "grounding_loss_ntok")
+        else:
+            _C.check(_C.lib().vlg_grounding_loss(_C.ptr(txt_c), _C.ptr(vis_c), _C.ptr(tm), _C.ptr(vm), _C.ptr(marg), _C.ptr(pen),
+                                                 _C.ptr(seg_of_v), n_seg, B, Q, V, d, dt, float(neg_inf), float(num_token),
+                                                 float(w_vis2txt), _C.ptr(ws), nbytes, _C.ptr(sums), _C.ptr(g_txt), _C.ptr(g_vis),
+                                                 _C.stream_of(txt_c)), "grounding_loss")
         ctx.save_for_backward(g_txt, g_vis)
         ctx.dtypes = (txt_feat.dtype, vis_feat.dtype)
         ctx.mark_non_differentiable(sums)
@@ -385,7 +439,9 @@ def grounding_loss_factor_ce(txt_feat, vis_feat, txt_mask, vis_mask, txt_margina
 
     Returns (total, sums) with sums = [txt2vis, vis2txt, total] (raw sums; the reference reports
     s / (s.detach() + 1e-6) * num_token for each, which total already contains).  `total` back-propagates to txt_feat
-    and vis_feat; txt_marginal is a constant, as in the reference (joint.py:251-268 builds it from detached scores)."""
+    and vis_feat; txt_marginal is a constant, as in the reference (joint.py:251-268 builds it from detached scores).
+    num_token: a host number, or a 0-d float32 tensor on the features' GPU -- read there by the kernel (vlg_grounding_loss_ntok: no
+    host synchronisation, and a captured graph follows the value); other tensors are read on the host as before."""
     txt_feat, vis_feat, txt_mask, vis_mask, txt_marginal = (_plain(t) for t in (txt_feat, vis_feat, txt_mask, vis_mask,
                                                                                 txt_marginal))
     _C.require_gpu(txt_feat, "grounding_loss_factor_ce")
@@ -394,6 +450,8 @@ def grounding_loss_factor_ce(txt_feat, vis_feat, txt_mask, vis_mask, txt_margina
         raise ValueError(f"grounding loss pairs caption b with image b: txt {tuple(txt_feat.shape)} vis {tuple(vis_feat.shape)}")
     if tuple(txt_marginal.shape) != (B, Q):
         raise ValueError(f"txt_marginal must be [B,Q]={(B, Q)}, got {tuple(txt_marginal.shape)}")
+    if _device_num_token(num_token) and num_token.device != txt_feat.device:
+        raise ValueError(f"grounding loss: num_token on {num_token.device}, features on {txt_feat.device}")
     return _GroundingLoss.apply(txt_feat, vis_feat, txt_mask, vis_mask, txt_marginal, pen, seg_of_v, num_token, vis2txt,
                                 neg_inf)
 

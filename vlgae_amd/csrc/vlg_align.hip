@@ -2419,10 +2419,11 @@ size_t vlg_grounding_loss_workspace(int B, int Q, int V) {
     return vlg::GroundPlan(B, Q, V).bytes;
 }
 
-int vlg_grounding_loss(const void* txt, const void* vis, const uint8_t* tmask, const uint8_t* vmask, const float* marginal,
-                       const float* pen, const uint8_t* seg_of_v, int n_seg, int B, int Q, int V, int d, int in_dtype,
-                       float neg_inf, float num_token, float w_vis2txt, void* ws, size_t ws_bytes, float* out_sums,
-                       float* g_txt, float* g_vis, void* stream) {
+// vlg_grounding_loss and vlg_grounding_loss_ntok: the normaliser as an argument or (num_token_dev != NULL) in device memory
+static int grounding_loss_impl(const void* txt, const void* vis, const uint8_t* tmask, const uint8_t* vmask, const float* marginal,
+                               const float* pen, const uint8_t* seg_of_v, int n_seg, int B, int Q, int V, int d, int in_dtype,
+                               float neg_inf, float num_token, const float* num_token_dev, float w_vis2txt, void* ws, size_t ws_bytes,
+                               float* out_sums, float* g_txt, float* g_vis, void* stream) {
     using namespace vlg;
     if (B < 1 || Q < 1 || V < 1 || d < 1)
         return set_error(VLG_ERR_SHAPE, "grounding_loss: bad shape B=%d Q=%d V=%d d=%d", B, Q, V, d);
@@ -2465,8 +2466,25 @@ int vlg_grounding_loss(const void* txt, const void* vis, const uint8_t* tmask, c
     else return set_error(VLG_ERR_SHAPE, "grounding_loss: d=%d (supported: 32, 64, 128)", d);
 #undef VLG_GA
     if (rc) return rc;
-    return launch_grounding_tail(txt, vis, tmask, vmask, marginal, B, Q, V, d, in_dtype, num_token, w_vis2txt, wsf, p, out_sums,
-                                 g_txt, g_vis, s);
+    return launch_grounding_tail(txt, vis, tmask, vmask, marginal, B, Q, V, d, in_dtype, num_token, num_token_dev, w_vis2txt, wsf, p,
+                                 out_sums, g_txt, g_vis, s);
+}
+
+int vlg_grounding_loss(const void* txt, const void* vis, const uint8_t* tmask, const uint8_t* vmask, const float* marginal,
+                       const float* pen, const uint8_t* seg_of_v, int n_seg, int B, int Q, int V, int d, int in_dtype,
+                       float neg_inf, float num_token, float w_vis2txt, void* ws, size_t ws_bytes, float* out_sums,
+                       float* g_txt, float* g_vis, void* stream) {
+    return grounding_loss_impl(txt, vis, tmask, vmask, marginal, pen, seg_of_v, n_seg, B, Q, V, d, in_dtype, neg_inf, num_token, nullptr,
+                               w_vis2txt, ws, ws_bytes, out_sums, g_txt, g_vis, stream);
+}
+
+int vlg_grounding_loss_ntok(const void* txt, const void* vis, const uint8_t* tmask, const uint8_t* vmask, const float* marginal,
+                            const float* pen, const uint8_t* seg_of_v, int n_seg, int B, int Q, int V, int d, int in_dtype,
+                            float neg_inf, const float* num_token, float w_vis2txt, void* ws, size_t ws_bytes, float* out_sums,
+                            float* g_txt, float* g_vis, void* stream) {
+    if (!num_token) return vlg::set_error(VLG_ERR_ARG, "grounding_loss_ntok: null num_token");
+    return grounding_loss_impl(txt, vis, tmask, vmask, marginal, pen, seg_of_v, n_seg, B, Q, V, d, in_dtype, neg_inf, 0.f, num_token,
+                               w_vis2txt, ws, ws_bytes, out_sums, g_txt, g_vis, stream);
 }
 
 size_t vlg_align_reduced_workspace(int B, int Q) {

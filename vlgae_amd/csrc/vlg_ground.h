@@ -14,9 +14,10 @@ struct GroundPlan {
     GroundPlan(int B, int Q, int V);
 };
 
-// Everything after the alignment kernel: the two cross-entropies, the scalar sums, the feature gradients.
+// Everything after the alignment kernel: the two cross-entropies, the scalar sums, the feature gradients.  num_token_dev: the
+// normaliser in device memory (NULL = the num_token argument).
 int launch_grounding_tail(const void* txt, const void* vis, const uint8_t* tmask, const uint8_t* vmask, const float* marg,
-                          int B, int Q, int V, int d, int in_dtype, float num_token, float w_v2t, float* ws,
+                          int B, int Q, int V, int d, int in_dtype, float num_token, const float* num_token_dev, float w_v2t, float* ws,
                           const GroundPlan& p, float* out_sums, float* g_txt, float* g_vis, hipStream_t s);
 
 // Scratch carving for vlg_align_reduced / _backward (gather_logit_reduced, joint.py:421-432): the forward leaves the max over

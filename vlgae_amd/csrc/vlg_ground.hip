@@ -210,9 +210,12 @@ __global__ __launch_bounds__(kCeTileThreads) void ground_ce_tile2_kernel(int n, 
 
 // sums = {txt2vis, vis2txt, total};  coef = {c1, c2}: d total / d txt2vis, d total / d vis2txt.
 // One wave: lane i adds partials i, i+64, ... in order, then a fixed xor tree (same bits every run).
+// num_token_dev (vlg_grounding_loss_ntok): the normaliser is read from device memory instead of the argument, so that a captured
+// graph serves every batch of its shape.
 __global__ __launch_bounds__(64) void ground_sum_kernel(const float* __restrict__ part1, const float* __restrict__ part2, int n1,
-                                                        int n2, float num_token, float w_v2t, float* __restrict__ sums,
-                                                        float* __restrict__ coef) {
+                                                        int n2, float num_token_arg, const float* __restrict__ num_token_dev, float w_v2t,
+                                                        float* __restrict__ sums, float* __restrict__ coef) {
+    const float num_token = num_token_dev ? *num_token_dev : num_token_arg;
     float t2v = 0.f, v2t = 0.f;
     for (int i = threadIdx.x; i < n1; i += 64) t2v += part1[i];
     for (int i = threadIdx.x; i < n2; i += 64) v2t += part2[i];
@@ -1542,7 +1545,7 @@ GroundPlan::GroundPlan(int B, int Q, int V) {
 }
 
 int launch_grounding_tail(const void* txt, const void* vis, const uint8_t* tmask, const uint8_t* vmask, const float* marg,
-                          int B, int Q, int V, int d, int in_dtype, float num_token, float w_v2t, float* ws,
+                          int B, int Q, int V, int d, int in_dtype, float num_token, const float* num_token_dev, float w_v2t, float* ws,
                           const GroundPlan& p, float* out_sums, float* g_txt, float* g_vis, hipStream_t s) {
     float *mV = ws + p.off_maxV, *mQ = ws + p.off_maxQ, *part = ws + p.off_part, *coef = ws + p.off_coef;
     const uint16_t* aV = reinterpret_cast<const uint16_t*>(ws + p.off_argV);
@@ -1598,7 +1601,8 @@ int launch_grounding_tail(const void* txt, const void* vis, const uint8_t* tmask
         hipLaunchKernelGGL(ground_ce_kernel<uint8_t>, dim3(B, y2), dim3(kCeThreads), 0, s, mQ, (size_t)V, (size_t)B * V, B, V, vmask, aQ,
                            vmask, tmask, Q, part2);
     }
-    hipLaunchKernelGGL(ground_sum_kernel, dim3(1), dim3(64), 0, s, part, part2, B * y1, B * y2, num_token, w_v2t, out_sums, coef);
+    hipLaunchKernelGGL(ground_sum_kernel, dim3(1), dim3(64), 0, s, part, part2, B * y1, B * y2, num_token, num_token_dev, w_v2t, out_sums,
+                       coef);
     if ((g_txt || g_vis) && in_dtype == VLG_BF16 && d == kGdD && Q <= 96 && V <= 65535 && !VLG_ENV("VLG_GROUND_SPARSE")) {
         // bf16 features, d = 128, up to 96 queries: the dense route on the matrix cores
         if (int rc = launch_bwd_dense(txt, vis, mV, aV, mQ, aQ, coef, B, Q, V, reinterpret_cast<uint16_t*>(ws + p.off_featT),

@@ -165,7 +165,8 @@ def forced_tree_score(md, ma, heads, lengths, big=1e4):
 # ----------------------------------------------------------------------------------------------------------------------------
 def build(B, L, R, dev, dtype=torch.bfloat16, d=128, h=256, seed=11, with_scorer=True, T=45, r=16, wiring="reference", given=None,
           alpha=0.5, use_pos_prior=True, vis2txt=1.0, p_drop=0.33, E=800, Et=32, H=256, nb=150, p_ff_drop=0.33, p_mid_drop=0.3,
-          factors=(), n_vis=2048, p_enc=0.33, pos_for=None, ln_eps=1e-5, ff_dtype=None, fused_ff=True, feature_grads=False):
+          factors=(), n_vis=2048, p_enc=0.33, pos_for=None, ln_eps=1e-5, ff_dtype=None, fused_ff=True, feature_grads=False, rng=None,
+          batch_on_device=False):
     """The step function of one training step at B sentences of <= L words and R region boxes per image.
 
     factors: which of ("rel", "attr", "img") the model adds to the object factor (cfg.add_rel / add_attr / add_image; the shipped
@@ -183,6 +184,12 @@ def build(B, L, R, dev, dtype=torch.bfloat16, d=128, h=256, seed=11, with_scorer
     p_ff_drop / p_mid_drop: the parser feed-forwards' dropout (shipped: 0.33 / 0.3; masks drawn per step; 0 = off, as in the fixtures).
     alpha / use_pos_prior / vis2txt: config/model/vlgae.yaml:62-67.  feature_grads: also return the gradient w.r.t. vis_box_feat (the
     reference does not compute it -- the region features are data; the parity tests do).
+    rng: the encoders.DeviceRng the step draws its dropout masks from (default: a new one seeded from `seed`; steps built for several
+    batch shapes can share one, so that the draws follow the step count).  batch_on_device: derive NOTHING from the batch's contents at
+    build time -- the first launch of every step(), vlg_step_batch_prepare, writes the vis mask, the POS prior table, num_token and the
+    loss coefficients into buffers the step owns, from the CURRENT contents of lengths / tag / box_mask.  Every given batch tensor and
+    parameter is used in place (copy the next batch of the same shape into them, update the parameters in place, call step() again); one
+    that would have to be copied -- another dtype or device, not contiguous -- raises ValueError.  Same values, bit for bit.
     Returns step(); step() -> (loss, {name: gradient}, ()).
 
     wiring="r3": round 3's chain (see the module docstring); `with_scorer` only matters there, and R is its V."""
@@ -194,6 +201,7 @@ def build(B, L, R, dev, dtype=torch.bfloat16, d=128, h=256, seed=11, with_scorer
     from vlgae_amd import align, encoders, langfeat, parser_ff, scorer
     N, Q = L + 1, 2 * (L + 1)
     given = dict(given or {})
+    given_ptrs = {k: t.data_ptr() for k, t in given.items() if torch.is_tensor(t)}
     factors = tuple(factors)
     if any(f not in ("rel", "attr", "img") for f in factors):
         raise ValueError(f"train_step.build: factors {factors}")
@@ -238,7 +246,8 @@ def build(B, L, R, dev, dtype=torch.bfloat16, d=128, h=256, seed=11, with_scorer
         # padding behind them (src/datamodule/task/vlparse.py:68-83) -- a PREFIX mask per image, n_i drawn from [0.6 R, R]
         n_box = torch.randint(max(1, (3 * R) // 5), R + 1, (B,), generator=g)
         box_mask = (torch.arange(R)[None] < n_box[:, None]).to(dev)
-    vmask = encoders.factor_mask(box_mask, add_rel, add_attr, add_image)       # vis_feat_unprune's mask (joint.py:140-170): data, built once per batch
+    if not batch_on_device:
+        vmask = encoders.factor_mask(box_mask, add_rel, add_attr, add_image)   # vis_feat_unprune's mask (joint.py:140-170): data, built once per batch
     fixed_drop = given.pop("drop") if "drop" in given else "draw"
     if fixed_drop is not None and not isinstance(fixed_drop, str):
         fixed_drop = fixed_drop.to(dev, torch.float32).permute(1, 0, 2).contiguous()      # [B,4,d]
@@ -248,24 +257,46 @@ def build(B, L, R, dev, dtype=torch.bfloat16, d=128, h=256, seed=11, with_scorer
         enc_drop = enc_drop.to(dev, torch.float32).contiguous()                           # [B,L,E]
     if given:
         raise ValueError(f"train_step.build: unknown given entries {sorted(given)}")
-    rng = encoders.DeviceRng(seed * 7919 + 17, dev)       # the counter-based dropout draws of the step (advanced on the device once per step)
+    if batch_on_device:
+        # a given tensor the step had to copy (another dtype / device, not contiguous) would keep its build-time values for ever: later
+        # batches copied into it and optimiser updates would be ignored without a word -- refuse it
+        used = dict(P, lengths=lengths, token=token, tag=tag, box_mask=box_mask)
+        copied = [k for k, p in given_ptrs.items() if k in used and used[k].data_ptr() != p]
+        if copied:
+            raise ValueError(f"train_step.build(batch_on_device=True): given {copied} would be copied, not used in place -- pass them "
+                             f"on {dev}, contiguous, in the step's types (parameters: `dtype`, ln_w / ln_b float32, emb / w_text / token_emb / "
+                             "root_emb / dec_emb / ff.*: `ff_dtype`; lengths / token / tag int64; box_mask bool)")
+    if rng is None:
+        rng = encoders.DeviceRng(seed * 7919 + 17, dev)   # the counter-based dropout draws of the step (advanced on the device once per step)
     if pos_for is None:
         pos_for = dict(obj=torch.tensor([0, 1, 2]), rel=torch.tensor([2, 3]), attr=torch.tensor([4]))
     pos_for = {k: t.to(dev) for k, t in pos_for.items()}
-    num_token = lengths.sum()                                     # a 0-d tensor like vp.num_token (var_pool.py:18)
-    num_token_f = float(num_token.item())
     names = sorted(k for k in P if P[k].requires_grad)
     leaves = [P[k] for k in names]
     aux = {}
-    # the POS prior table (joint.py:446-470) is a function of the batch's tags only -- data, like the masks: built once per batch
-    pen = seg = None
-    if use_pos_prior:
-        pen, seg = align.grounding_prior(tag, factor_names, vis_split, pos_for, Q)
-    # loss = (alpha mt + (1 - alpha) dep) / (num_token + 1e-12), dep = -sum_b max_b: two per-batch coefficients.  They seed the
-    # backward pass directly (autograd.grad's grad_outputs), so the scalar arithmetic of the combination has no adjoint launches.
-    coef = (torch.tensor([alpha, -(1.0 - alpha)], dtype=torch.float32, device=dev) / (num_token.to(torch.float32) + 1e-12))
-    c_mt, c_max = coef[0], coef[1]
-    seed_max = c_max.repeat(B)
+    if batch_on_device:
+        # buffers the first launch of every step fills from the batch tensors' current contents (vlg_step_batch_prepare)
+        pos_for = {k: t.to(torch.int64).contiguous() for k, t in pos_for.items()}
+        lengths, tag = lengths.contiguous(), tag.contiguous()
+        vmask = torch.empty((B, V), dtype=torch.bool, device=dev)
+        pen = torch.empty((B, Q, len(vis_split)), dtype=torch.float32, device=dev) if use_pos_prior else None
+        seg = align.segment_map(vis_split, dev) if use_pos_prior else None      # a function of the layout alone
+        num_token = num_token_f = torch.empty((), dtype=torch.float32, device=dev)   # read by the grounding loss's kernel
+        coef = torch.empty(2, dtype=torch.float32, device=dev)
+        c_mt = coef[0]
+        seed_max = torch.empty(B, dtype=torch.float32, device=dev)
+    else:
+        num_token = lengths.sum()                                     # a 0-d tensor like vp.num_token (var_pool.py:18)
+        num_token_f = float(num_token.item())
+        # the POS prior table (joint.py:446-470) is a function of the batch's tags only -- data, like the masks: built once per batch
+        pen = seg = None
+        if use_pos_prior:
+            pen, seg = align.grounding_prior(tag, factor_names, vis_split, pos_for, Q)
+        # loss = (alpha mt + (1 - alpha) dep) / (num_token + 1e-12), dep = -sum_b max_b: two per-batch coefficients.  They seed the
+        # backward pass directly (autograd.grad's grad_outputs), so the scalar arithmetic of the combination has no adjoint launches.
+        coef = (torch.tensor([alpha, -(1.0 - alpha)], dtype=torch.float32, device=dev) / (num_token.to(torch.float32) + 1e-12))
+        c_mt, c_max = coef[0], coef[1]
+        seed_max = c_max.repeat(B)
     T_, H_ = P["token_emb"].shape[0], P["ff.head_ff.linear.weight"].shape[0]
 
     def draw_masks():
@@ -290,6 +321,8 @@ def build(B, L, R, dev, dtype=torch.bfloat16, d=128, h=256, seed=11, with_scorer
         """forward + backward; returns (reduced loss, gradients by leaf name, ()).  stage_hook (optional) is called from inside the
         backward pass once the adjoints of the DP and of the grounding loss have run (the cotangent of `txt` exists) -- where a
         data-parallel trainer starts reducing its first gradient bucket."""
+        if batch_on_device:
+            align.step_batch_prepare(lengths, tag, box_mask, factors, pos_for, Q, alpha, vmask, pen, num_token, coef, seed_max)
         drop, ff_masks = draw_masks()
         d0, d3 = (None, None) if drop is None else (drop[:, 0:1], drop[:, 1:4])
         # ---- JointModelBase.forward, base.py:229 / :68: the two trainable encoders on the frozen features ----
