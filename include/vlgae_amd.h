@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-enum { VLG_F32 = 0, VLG_BF16 = 1 };
+enum { VLG_F32 = 0, VLG_BF16 = 1, VLG_F64 = 2 /* rule tables of vlg_dmv1o_gold_rules only */ };
 enum { VLG_SEMIRING_LOG = 0, VLG_SEMIRING_MAX = 1 };
 enum {
     VLG_OP_DMV1O_INSIDE = 0,
@@ -588,6 +588,32 @@ int vlg_dmv1o_marginals_viterbi(const void* dec, const void* attach, const int64
  *   elements per sentence; either side may be empty (n = 0, pointers then ignored). */
 int vlg_scale_counts(const float* counts_a, const float* counts_b, const float* g, int g_stride, int B, int n_a, int n_b,
                      int out_dtype, void* out_a, void* out_b, void* stream);
+
+/* The gold tree's rule counts -- the parser's rule-supervised initialisation epochs (init_method 'y', src/model/ldndmv.py:153-159,
+ * 262-275): generate_rule_1o (src/model/dmv_helper/good_init_nn.py:34-77) per sentence from its `arc` field, padded like LinearPadder /
+ * SquarePadder, and enll = -(dec_rule . dec) - (attach_rule . attach) - (root_rule . root).  One workgroup per sentence, no atomics.
+ *   arc [B, ld_arc] int64: arc[b,c] = 1-based head of word c, 0 = the root; entries at c >= lengths[b] are not read.
+ * Word c with head h = arc[c]-1 is a LEFT child when c < h, else RIGHT; valence NOCHILD when it is h's outermost child on that side.
+ *   h >= 0: attach[h,c,v] += 1, dec[h,dir,v,GO] += 1;  every c: dec[c,LEFT|RIGHT, NOCHILD iff no child on that side, STOP] += 1;
+ *   root[c0] = 1 for the first c0 with arc 0;  every root child c: dec[n-1,RIGHT, c == n-1 ? NOCHILD : HASCHILD, GO] += 1 (the
+ *   reference's decision[-1], reproduced).  Non-projective trees, cycles, several roots and self-loops are counted as written.
+ * INVALID sentence -- an arc outside [0, n], no arc 0, or a length outside [1, L] (tables) / [1, N-1] (score), or above ld_arc: zero
+ * counts and score NaN (as vlg_dmv1o_rules treats a bad token id).
+ *
+ * vlg_dmv1o_gold_rules: dec_rule [B,L,2,2,2], attach_rule [B,L,L,2], root_rule [B,L] in out_dtype VLG_F32 or VLG_F64, zero past n: the
+ *   reference's padded `dec_rule` / `attach_rule` / `root_rule` fields bit for bit.  1 <= L <= 254.
+ * vlg_dmv1o_gold_score: score [B] = sum of count * potential over the ROOT-MERGED potentials (distributions.py:253-265: dec = md[:,1:],
+ *   attach = ma[:,1:,1:], root = ma[:,0,1:,NOCHILD]), merged_dec [B,N,2,2,2] / merged_attach [B,N,N,2] in in_dtype (VLG_F32 / VLG_BF16),
+ *   N <= 255.  Only positions with a nonzero count are read (the merged charts' -inf / -1e20 fills never meet a zero count); float64
+ *   accumulation in a fixed order.
+ * vlg_dmv1o_gold_score_backward: grad_dec [B,N,2,2,2], grad_attach [B,N,N,2] = g[b*g_stride] * counts in the merged layout (g_stride 1:
+ *   g [B]; 0: one scalar), out_dtype VLG_F32 / VLG_BF16; every element written (no memset needed). */
+int vlg_dmv1o_gold_rules(const int64_t* arc, int ld_arc, const int64_t* lengths, int B, int L, int out_dtype, void* dec_rule, void* attach_rule,
+                         void* root_rule, void* stream);
+int vlg_dmv1o_gold_score(const void* merged_dec, const void* merged_attach, const int64_t* arc, int ld_arc, const int64_t* lengths, int B, int N,
+                         int in_dtype, float* score, void* stream);
+int vlg_dmv1o_gold_score_backward(const int64_t* arc, int ld_arc, const int64_t* lengths, int B, int N, const float* g, int g_stride,
+                                  int out_dtype, void* grad_dec, void* grad_attach, void* stream);
 
 /* ---- Data feed (host code; no device work, no stream).  SURVEY.md section 8 row f4. ----
  *

@@ -11,7 +11,7 @@ import torch
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VLGAE_AMD_LIB") or os.path.join(_PKG, "_lib", "libvlgae_amd.so")
 
-F32, BF16 = 0, 1
+F32, BF16, F64 = 0, 1, 2
 SEMIRING_LOG, SEMIRING_MAX = 0, 1
 OP_DMV1O_INSIDE, OP_DMV1O_INSIDE_OUTSIDE, OP_DEPTREE_INSIDE, OP_DEPTREE_INSIDE_OUTSIDE = 0, 1, 2, 3
 
@@ -124,6 +124,9 @@ SIGNATURES = {
                                           _vp, _i, _vp, _vp, _vp]),
     "vlg_dmv1o_viterbi": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vlg_scale_counts": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "vlg_dmv1o_gold_rules": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "vlg_dmv1o_gold_score": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp]),
+    "vlg_dmv1o_gold_score_backward": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "vlg_feed_kmeans": (_i, [_vp, ctypes.c_int64, _vp, _i, _i, _vp, _vp, _vp]),
     "vlg_feed_batches": (_i, [_vp, ctypes.c_int64, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "vlg_feed_npy_shape": (_i, [ctypes.c_char_p, _vp, _vp]),

@@ -6,6 +6,7 @@ Sub-modules
     langfeat       `lang_feat_max_tree` / `lang_feat_word_only` as fused stages (encoders with SharedDropout masks, arc encoder)
     scorer         score construction feeding the DP (factorised-bilinear scores -> merged potentials)
     parser_ff      the parser's feed-forwards in front of it (head_ff / mid_ff / scorer projections)
+    rules1o        the gold tree's rule counts, score and adjoint (the parser's rule-supervised initialisation epochs)
     vis_encoder    the visual encoder's pairwise relation features
     feed           token-budget batch sampler and region-feature collate (host C++)
     dist           batch sharding + the single RCCL gradient all-reduce

@@ -132,13 +132,14 @@ class DMV1o(StructDistribution):
         dec, attach = self.log_potentials
         return F.dmv1o_decode(dec, attach, self.lengths)[1]
 
-    def marginals_and_heads(self, keep_viterbi=False):
+    def marginals_and_heads(self, keep_viterbi=False, keep_partition=False):
         """Extension: (`marginals`, `argmax_heads`) with the two DPs overlapped on two HIP streams -- the pair
         lang_feat_max_tree asks for every step (joint.py:251-258).  keep_viterbi=True: the Viterbi pass also produces the
         tree counts and is remembered, so a later `DMV1o(same potentials).max` (the parser's `-max` loss, ldndmv.py:277-281)
-        and its backward launch nothing (see functional.dmv1o_marginals_and_heads)."""
+        and its backward launch nothing (see functional.dmv1o_marginals_and_heads).  keep_partition=True: the same for `.partition` (the
+        parser's marginal loss, ldndmv.py:280-281): the inside-outside pass also writes the dec counts and is remembered."""
         dec, attach = self.log_potentials
-        _, gatt, heads = F.dmv1o_marginals_and_heads(dec, attach, self.lengths, keep_viterbi)
+        _, gatt, heads = F.dmv1o_marginals_and_heads(dec, attach, self.lengths, keep_viterbi, keep_partition)
         return gatt, heads
 
     def marginals_and_heads_async(self, keep_viterbi=False):

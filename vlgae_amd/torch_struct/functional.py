@@ -185,8 +185,29 @@ def _viterbi_lookup(dec, attach, lengths):
 
 
 def viterbi_forget():
-    """Drop the remembered Viterbi result (and the references that keep its potentials alive)."""
+    """Drop the remembered Viterbi and partition results (and the references that keep their potentials alive)."""
     _VITERBI.clear()
+    _PARTITION.clear()
+
+
+# The same for the Log semiring: with the marginal loss (`viterbi_training: false`, ldndmv.py:280-281) the parser takes
+# `-DMV1o(...).partition.sum()` of the potentials whose inside-outside pass lang_feat_max_tree has just run for the arc marginals
+# (joint.py:251-255).  `marginals_and_heads(keep_partition=True)` remembers (logZ, grad_dec, grad_attach) under the key discipline above,
+# so that `.partition` and its backward launch no DP.
+_PARTITION = {}
+
+
+def _partition_remember(dec, attach, lengths, result):
+    _PARTITION[dec.device] = (_viterbi_key(dec, attach, lengths), (dec.detach(), attach.detach(), lengths), result)
+
+
+def _partition_lookup(dec, attach, lengths):
+    if not isinstance(lengths, torch.Tensor):
+        return None
+    hit = _PARTITION.get(dec.device)
+    if hit is None or hit[0] != _viterbi_key(dec, attach, lengths):
+        return None
+    return hit[2]
 
 
 def deptree_decode(arc, lengths=None):
@@ -285,9 +306,13 @@ class _DMV1oSum(torch.autograd.Function):
     def forward(ctx, dec, attach, lengths, semiring):
         want = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         hit = _viterbi_lookup(dec, attach, lengths) if semiring == _C.SEMIRING_MAX and dec.dtype != torch.float64 else None
+        phit = _partition_lookup(dec, attach, lengths) if semiring == _C.SEMIRING_LOG and dec.dtype != torch.float64 else None
         if hit is not None:   # this step's Viterbi pass already ran on these very values (marginals_and_heads(keep_viterbi=True))
             best, gdec, gatt, _ = hit
             logZ = best.view(-1, 1)
+        elif phit is not None:   # ... or its inside-outside pass, with the dec counts (marginals_and_heads(keep_partition=True))
+            lz, gdec, gatt = phit
+            logZ = lz.view(-1, 1)
         else:
             logZ, gdec, gatt = dmv1o_run(dec, attach, lengths, semiring, want, logZ_shape=(dec.shape[0], 1))   # [B,1], helpers.py:116
         if want:
@@ -410,7 +435,7 @@ def dmv1o_merge_autograd(dec, attach, root, one=0.0, zero=NEGINF):
 _SIDE_STREAMS = {}
 
 
-def _marginals_viterbi_one_launch(dec, attach, lengths, keep_viterbi):
+def _marginals_viterbi_one_launch(dec, attach, lengths, keep_viterbi, keep_partition=False):
     """Both DPs of `dmv1o_marginals_and_heads` as ONE launch on the current stream (vlg_dmv1o_marginals_viterbi: grid (B, 2), the two
     workgroups of a sentence share a CU): sentences short enough that both passes keep their charts in LDS (N <= 44: twice the larger footprint within 160 KB).  No side
     stream, no events: ~15 us less than the two-stream form at B = 256, L = 40 and nothing for a HIP-graph capture to fork."""
@@ -430,15 +455,18 @@ def _marginals_viterbi_one_launch(dec, attach, lengths, keep_viterbi):
     heads = torch.empty((B, N), dtype=torch.int64, device=dev)
     vdec = torch.empty((B, N, 2, 2, 2), dtype=torch.float32, device=dev) if keep_viterbi else None
     vatt = torch.empty((B, N, N, 2), dtype=torch.float32, device=dev) if keep_viterbi else None
-    _C.check(_C.lib().vlg_dmv1o_marginals_viterbi(_C.ptr(dec_c), _C.ptr(att_c), _C.ptr(lengths), B, N, dt, _C.ptr(logZ), None, _C.ptr(gatt),
+    gdec = torch.empty((B, N, 2, 2, 2), dtype=torch.float32, device=dev) if keep_partition else None
+    _C.check(_C.lib().vlg_dmv1o_marginals_viterbi(_C.ptr(dec_c), _C.ptr(att_c), _C.ptr(lengths), B, N, dt, _C.ptr(logZ), _C.ptr(gdec), _C.ptr(gatt),
                                                   _C.ptr(best), _C.ptr(vdec), _C.ptr(vatt), _C.ptr(heads), _C.stream_of(dec)),
              "dmv1o_marginals_viterbi")
     if keep_viterbi:
         _viterbi_remember(dec, attach, lengths, (best, vdec, vatt, heads))
+    if keep_partition:
+        _partition_remember(dec, attach, lengths, (logZ, gdec, gatt))
     return logZ, gatt, heads
 
 
-def dmv1o_marginals_and_heads(dec, attach, lengths, keep_viterbi=False):
+def dmv1o_marginals_and_heads(dec, attach, lengths, keep_viterbi=False, keep_partition=False):
     """What lang_feat_max_tree needs from one sentence batch (joint.py:251-258): the arc marginals
     d logZ / d attach AND the Viterbi heads.  The two are independent DPs over the same potentials; at one
     workgroup per CU each leaves most of the machine idle and their LDS footprints (78 KB + 49 KB at N = 41) fit one
@@ -447,10 +475,14 @@ def dmv1o_marginals_and_heads(dec, attach, lengths, keep_viterbi=False):
 
     keep_viterbi=True (training with `viterbi_training`, ldndmv.py:277-281): the side-stream launch is the full Viterbi pass
     (best score + tree counts + heads, 67 us instead of the 57 us walk) and its result is remembered, so the `DMV1o(...).max`
-    that the loss takes of the same potentials later in the step launches nothing."""
+    that the loss takes of the same potentials later in the step launches nothing.
+
+    keep_partition=True (training with the marginal loss, `viterbi_training: false`, ldndmv.py:280-281): the inside-outside pass also
+    writes the dec counts and (logZ, grad_dec, grad_attach) is remembered, so a later `DMV1o(same potentials).partition` and its
+    backward launch nothing either."""
     _C.require_gpu(dec, "dmv1o_marginals_and_heads")
     if dec.dim() == 5 and _C.lib().vlg_dmv1o_marginals_viterbi_supported(dec.shape[1]):
-        return _marginals_viterbi_one_launch(dec, attach, lengths, keep_viterbi)
+        return _marginals_viterbi_one_launch(dec, attach, lengths, keep_viterbi, keep_partition)
     cur = torch.cuda.current_stream(dec.device)
     side = _SIDE_STREAMS.get(dec.device)
     if side is None:
@@ -462,16 +494,17 @@ def dmv1o_marginals_and_heads(dec, attach, lengths, keep_viterbi=False):
     B, N = dec.shape[:2]
     best = torch.empty(B, dtype=torch.float32, device=dec.device)
     heads = torch.empty((B, N), dtype=torch.int64, device=dec.device)
+    if keep_viterbi or keep_partition:
+        lengths = _lengths(lengths, B, dec.device)
     if keep_viterbi:
         vdec = torch.empty((B, N, 2, 2, 2), dtype=torch.float32, device=dec.device)
         vatt = torch.empty((B, N, N, 2), dtype=torch.float32, device=dec.device)
-        lengths = _lengths(lengths, B, dec.device)
     # The potentials are produced on the current stream: the side stream waits for an event recorded HERE, and the longer of the
     # two launches (the Log-semiring inside-outside pass) is enqueued first -- it starts ~6 us earlier than when it followed the
     # side-stream launch, and the pair ends when it does.
     ready = torch.cuda.Event()
     ready.record(cur)
-    logZ, _, gatt = dmv1o_run(dec, attach, lengths, _C.SEMIRING_LOG, True, want_dec=False)
+    logZ, gdec, gatt = dmv1o_run(dec, attach, lengths, _C.SEMIRING_LOG, True, want_dec=keep_partition)
     side.wait_event(ready)
     with torch.cuda.stream(side):
         if keep_viterbi:
@@ -481,6 +514,8 @@ def dmv1o_marginals_and_heads(dec, attach, lengths, keep_viterbi=False):
     cur.wait_stream(side)
     if keep_viterbi:
         _viterbi_remember(dec, attach, lengths, (best, vdec, vatt, heads))
+    if keep_partition:
+        _partition_remember(dec, attach, lengths, (logZ, gdec, gatt))
     return logZ, gatt, heads
 
 

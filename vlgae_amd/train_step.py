@@ -32,7 +32,13 @@ The SAME function is what
       gather_logit_simple          :406-419   } never materialised: alignment maxima + arg-max on the matrix cores,
   DependencyBoxRel.loss            :693-711   }
       loss_grounding_factor_ce     :439-491   } POS prior (use_pos_prior: true), both cross-entropies, vis2txt = 1          -> align.grounding_loss_factor_ce
-      DiscriminativeNDMV.loss      ldndmv.py:277-281  viterbi_training: -DMV1o(potentials).max.sum() (the step's one Viterbi pass is reused)
+      DiscriminativeNDMV.loss      ldndmv.py:260-285, by `dep_loss`:
+                                     "viterbi"    (viterbi_training, after the init epochs) -DMV1o(potentials).max.sum() (the step's one
+                                                  Viterbi pass is reused)
+                                     "gold_rules" (the first init_epoch epochs of init_method 'y', :262-275) enll = -(rule counts of the
+                                                  batch's gold `arc` . potentials), rules1o.gold_rule_score
+                                     "partition"  (viterbi_training: false, :280-281) -DMV1o(potentials).partition.sum() (the
+                                                  inside-outside pass of lang_feat_max_tree is reused)
       alpha * mt_loss + (1 - alpha) * dep_loss, alpha = grounding_interpolation = 0.5 (config/model/vlgae.yaml:67)
   reduce_loss('token')             src/utility/fn.py:50-56 (src/pipeline.py:124,249-250): / (num_token + 1e-12)
   loss.backward()                  every adjoint of the above
@@ -49,6 +55,7 @@ import torch
 import torch.nn.functional as F
 
 SLOPE = 0.01           # nn.LeakyReLU() default, nn/common.py:31
+DEP_LOSSES = ("viterbi", "gold_rules", "partition")
 FF_MODULES = ("head_ff", "child_ff", "root_ff", "dec_ff", "mid_ff", "attach_scorer", "dec_scorer", "root_scorer")
 
 
@@ -166,7 +173,7 @@ def forced_tree_score(md, ma, heads, lengths, big=1e4):
 def build(B, L, R, dev, dtype=torch.bfloat16, d=128, h=256, seed=11, with_scorer=True, T=45, r=16, wiring="reference", given=None,
           alpha=0.5, use_pos_prior=True, vis2txt=1.0, p_drop=0.33, E=800, Et=32, H=256, nb=150, p_ff_drop=0.33, p_mid_drop=0.3,
           factors=(), n_vis=2048, p_enc=0.33, pos_for=None, ln_eps=1e-5, ff_dtype=None, fused_ff=True, feature_grads=False, rng=None,
-          batch_on_device=False):
+          batch_on_device=False, dep_loss="viterbi"):
     """The step function of one training step at B sentences of <= L words and R region boxes per image.
 
     factors: which of ("rel", "attr", "img") the model adds to the object factor (cfg.add_rel / add_attr / add_image; the shipped
@@ -192,13 +199,31 @@ def build(B, L, R, dev, dtype=torch.bfloat16, d=128, h=256, seed=11, with_scorer
     that would have to be copied -- another dtype or device, not contiguous -- raises ValueError.  Same values, bit for bit.
     Returns step(); step() -> (loss, {name: gradient}, ()).
 
+    dep_loss: the parser's loss (DiscriminativeNDMV.loss, ldndmv.py:260-285).  "viterbi": -max of the step's potentials (viterbi_training,
+    after the initialisation epochs; the default).  "gold_rules": the rule-supervised initialisation epochs (init_method 'y', the first
+    init_epoch epochs): -score of the gold tree given as the batch tensor `arc` [B,L] int64 (1-based heads, 0 = root; given["arc"],
+    required, used in place under batch_on_device), rules1o.gold_rule_score; lang_feat_max_tree then keeps no Viterbi pass and
+    `forced_heads` only changes the tree it reads.  "partition": the marginal loss (viterbi_training: false), -logZ of the step's
+    potentials, reusing lang_feat_max_tree's inside-outside pass.  Every mode seeds its per-sentence score with the same coefficient
+    -(1 - alpha) / num_token; step.last["dep_score"] holds it.
+    Returns step(); step() -> (loss, {name: gradient}, ()).
+
     wiring="r3": round 3's chain (see the module docstring); `with_scorer` only matters there, and R is its V."""
+    if dep_loss not in DEP_LOSSES:
+        raise ValueError(f"train_step.build: dep_loss {dep_loss!r} (one of {DEP_LOSSES})")
+    has_arc = bool(given) and "arc" in given
+    if dep_loss == "gold_rules" and not has_arc:
+        raise ValueError("train_step.build(dep_loss='gold_rules') needs the batch's gold trees: given['arc'] [B,L] int64 (1-based heads, 0 = root)")
+    if has_arc and dep_loss != "gold_rules":
+        raise ValueError(f"train_step.build: given['arc'] is only read with dep_loss='gold_rules' (got dep_loss={dep_loss!r})")
+    if wiring == "r3" and dep_loss != "viterbi":
+        raise ValueError("train_step.build: wiring='r3' has the Viterbi loss only")
     if wiring == "r3":
         return _build_r3(B, L, R, dev, dtype, d, h, seed, with_scorer, T, r)
     if wiring != "reference":
         raise ValueError(wiring)
     import vlgae_amd.torch_struct as ts
-    from vlgae_amd import align, encoders, langfeat, parser_ff, scorer
+    from vlgae_amd import align, encoders, langfeat, parser_ff, rules1o, scorer
     N, Q = L + 1, 2 * (L + 1)
     given = dict(given or {})
     given_ptrs = {k: t.data_ptr() for k, t in given.items() if torch.is_tensor(t)}
@@ -252,6 +277,9 @@ def build(B, L, R, dev, dtype=torch.bfloat16, d=128, h=256, seed=11, with_scorer
     if fixed_drop is not None and not isinstance(fixed_drop, str):
         fixed_drop = fixed_drop.to(dev, torch.float32).permute(1, 0, 2).contiguous()      # [B,4,d]
     forced_heads = given.pop("heads").to(dev, torch.int64) if "heads" in given else None
+    arc = given.pop("arc").to(dev, torch.int64).contiguous() if "arc" in given else None
+    if arc is not None and tuple(arc.shape) != (B, L):
+        raise ValueError(f"train_step.build: given['arc'] must be [B, L] = {(B, L)}, got {tuple(arc.shape)}")
     enc_drop = given.pop("enc_drop") if "enc_drop" in given else "draw"
     if enc_drop is not None and not isinstance(enc_drop, str):
         enc_drop = enc_drop.to(dev, torch.float32).contiguous()                           # [B,L,E]
@@ -260,12 +288,12 @@ def build(B, L, R, dev, dtype=torch.bfloat16, d=128, h=256, seed=11, with_scorer
     if batch_on_device:
         # a given tensor the step had to copy (another dtype / device, not contiguous) would keep its build-time values for ever: later
         # batches copied into it and optimiser updates would be ignored without a word -- refuse it
-        used = dict(P, lengths=lengths, token=token, tag=tag, box_mask=box_mask)
+        used = dict(P, lengths=lengths, token=token, tag=tag, box_mask=box_mask, **({} if arc is None else dict(arc=arc)))
         copied = [k for k, p in given_ptrs.items() if k in used and used[k].data_ptr() != p]
         if copied:
             raise ValueError(f"train_step.build(batch_on_device=True): given {copied} would be copied, not used in place -- pass them "
                              f"on {dev}, contiguous, in the step's types (parameters: `dtype`, ln_w / ln_b float32, emb / w_text / token_emb / "
-                             "root_emb / dec_emb / ff.*: `ff_dtype`; lengths / token / tag int64; box_mask bool)")
+                             "root_emb / dec_emb / ff.*: `ff_dtype`; lengths / token / tag / arc int64; box_mask bool)")
     if rng is None:
         rng = encoders.DeviceRng(seed * 7919 + 17, dev)   # the counter-based dropout draws of the step (advanced on the device once per step)
     if pos_for is None:
@@ -351,12 +379,17 @@ def build(B, L, R, dev, dtype=torch.bfloat16, d=128, h=256, seed=11, with_scorer
         md, ma = scorer.ndmv_potentials(x1, x2, y1, y2, root_rule, token)
         # ---- DependencyBoxRel._vis_forward, joint.py:677-691: the UN-fused x; the potentials are constants of this stage (:252-253) ----
         txt, tmask, tmarg = langfeat.lang_feat_max_tree(None, lengths, md.detach(), ma.detach(), None, None, P["w1"],
-                                                        P["w2"], P["b"], keep_viterbi=True, drop=d3, aux=aux, pre=pre, heads=step.forced_heads)
+                                                        P["w2"], P["b"], keep_viterbi=dep_loss == "viterbi", drop=d3, aux=aux, pre=pre,
+                                                        heads=step.forced_heads, keep_partition=dep_loss == "partition")
         if stage_hook is not None:
             txt.register_hook(lambda g_: stage_hook())
         # ---- DependencyBoxRel.loss, joint.py:693-711 ----
         mt, sums = align.grounding_loss_factor_ce(txt, vis_feat, tmask, vmask, tmarg, num_token_f, vis2txt, pen, seg)
-        if step.forced_heads is None:
+        if dep_loss == "gold_rules":
+            mx = rules1o.gold_rule_score(md, ma, arc, lengths)    # ldndmv.py:262-275: enll = -(gold rule counts . potentials)
+        elif dep_loss == "partition":
+            mx = ts.DMV1o([md, ma], lengths).partition            # ldndmv.py:280-281: dep = -partition.sum(); lang_feat_max_tree's pass is reused
+        elif step.forced_heads is None:
             mx = ts.DMV1o([md, ma], lengths).max                  # ldndmv.py:277-281: dep = -max.sum(); lang_feat_max_tree's Viterbi pass is reused
         else:
             mx = forced_tree_score(md, ma, step.forced_heads, lengths)   # teacher forcing: the given tree's score in place of the best tree's
@@ -368,10 +401,10 @@ def build(B, L, R, dev, dtype=torch.bfloat16, d=128, h=256, seed=11, with_scorer
         # capture makes torch 2.10 / ROCm 7 crash in capture_end
         step.last = {k: (v.detach() if torch.is_tensor(v) else v) for k, v in dict(
             enc_x=enc_x, vis_mid=vis_mid, x_fused=x_f, merged_dec=md, merged_attach=ma, txt=txt, txt_mask=tmask, txt_marginal=tmarg, vis_feat=vis_feat, sums=sums,
-            viterbi_max=mx, mt_loss=mt, heads=aux.get("heads")).items()}
+            viterbi_max=mx if dep_loss == "viterbi" else None, dep_score=mx, mt_loss=mt, heads=aux.get("heads")).items()}
         return loss, dict(zip(names, grads)), ()
 
-    step.names, step.P, step.lengths, step.wiring = names, P, lengths, wiring
+    step.names, step.P, step.lengths, step.wiring, step.dep_loss, step.arc = names, P, lengths, wiring, dep_loss, arc
     # Teacher forcing (parity tests only; None = the reference's behaviour): with a tree given, lang_feat_max_tree reads ITS parents and
     # marginals, and the parser's loss is -score(that tree) instead of -max -- the same function of the parameters the reference
     # differentiates when its own Viterbi tree is that tree (joint.py:256-273 and ldndmv.py:277-281 treat the tree as a constant).  A bf16
