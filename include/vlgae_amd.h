@@ -93,6 +93,13 @@ int vlg_dmv1o_decode(const void* dec, const void* attach, const int64_t* lengths
 int vlg_deptree_decode(const void* arc, const int64_t* lengths, int B, int N, int in_dtype, float* best_score,
                        int64_t* heads, void* ws, size_t ws_bytes, void* stream);
 
+/* The MBR decode of ldndmv.py:294-299 straight from the DMV1o arc marginals: DependencyCRF(marginals.sum(-1)).argmax.  marginals
+ * [B,N,N,2] float32 (head, child, valence), as vlg_dmv1o_inside_outside / vlg_dmv1o_marginals_viterbi write grad_attach; the valence sum
+ * is taken as the scores are loaded (no [B,N,N] intermediate).  heads / best_score as vlg_deptree_decode gives them on
+ * `marginals.sum(-1)`, bit for bit.  Workspace as for VLG_OP_DEPTREE_INSIDE_OUTSIDE, semiring 1. */
+int vlg_deptree_mbr_decode(const float* marginals, const int64_t* lengths, int B, int N, float* best_score, int64_t* heads, void* ws,
+                           size_t ws_bytes, void* stream);
+
 /* The DMV DP fed directly from the scorer's rule tables.  Folds into the kernel's load
  * stage what DiscriminativeNDMV._forward does between the scorer and the DP (src/model/ldndmv.py:189-209):
  *   attach[b,h,c,v] = attach_rule[b, h, token[b,c], dir(h,c), v]   (gather by the child's token + tril/triu select)
@@ -615,6 +622,36 @@ int vlg_dmv1o_gold_score(const void* merged_dec, const void* merged_attach, cons
 int vlg_dmv1o_gold_score_backward(const int64_t* arc, int ld_arc, const int64_t* lengths, int B, int N, const float* g, int g_stride,
                                   int out_dtype, void* grad_dec, void* grad_attach, void* stream);
 
+/* ---- Evaluation metrics on the device: the `metric.update` of Pipeline.validation_step (src/pipeline.py:132-143) for one batch ----
+ * DependencyParsingMetric, FactorImageMatchingMetric and BoxRelMatchingMetric (src/utility/metric.py:18-61, 64-83, 108-208) as integer
+ * counts, accumulated INTO counters [VLG_EVAL_SLOTS] int64 (the caller zeroes them at the start of an epoch; consecutive batches are
+ * ordered by the stream).  Two launches: one workgroup per sentence writes its partial counts to a workspace row, one workgroup adds
+ * the rows in a fixed order.  No float accumulation except the loss sum.
+ *   pred_arc [B, ld_pred >= L] int64: predicted 1-based head of word t (0 = root / padding); gold_arc [B,L] int64; mask [B,L] uint8
+ *   (the batch's punct_mask; NULL = vp.mask, the length mask t < lengths[b]); lengths [B] int64.
+ *   Parsing: correct_arcs += #(pred == gold & mask), total += #mask, n_ucm += #{b: every masked word correct}, n += B.
+ *   factor2img [B,Q] int32 with Q = 2 (L + 1) (or NULL: skipped): the kept query rows of sentence b are 1..n_b and L+2..L+1+n_b,
+ *   n_b = lengths[b] clamped to [0,L]; f2i_total += 2 n_b, f2i_correct += #{kept q: factor2img[b,q] == b}.
+ *   Box / relation (all of vis_box [B,R,4], sg_box [B,L,8], sg_type [B,L] int64, sg_mask [B,L] uint8 and top5 [B,Q,5] int32, or none of
+ *   them: skipped): the scored tokens of sentence b are t < m_b = #mask[b], token t = query row t + 1, its predictions the first
+ *   min(5, V) columns of top5, V = R + (add_rel ? R*R : 0) + (add_attr ? R : 0) + (add_image ? 1 : 0); column -> (type, box pair):
+ *   obj 1 (i,i) | rel 3 (i / R, i % R) | attr 2 (i,i) | img 0 (0,0).  IoU in IEEE float32 in the operation order of _one_by_one_iou,
+ *   compared > 0.5 (0 / 0 = NaN compares false).  Every prediction of every scored token takes part, for any m_b >= 1 (the reference
+ *   raises for m_b < min(5, V), metric.py:171).  total_obj / attr / rel count sg_type over all [B,L]; processed_token += sum(mask).
+ *   loss (or NULL): one float32, the batch's reduced loss; loss_sum += (double)*loss in batch order, n_batches += 1 either way.
+ * Workspace: vlg_eval_metrics_workspace(B) bytes.  Shapes, nulls and the workspace are checked before any launch. */
+enum {
+    VLG_EVAL_CORRECT_ARCS = 0, VLG_EVAL_TOTAL = 1, VLG_EVAL_N_UCM = 2, VLG_EVAL_N = 3, VLG_EVAL_F2I_CORRECT = 4, VLG_EVAL_F2I_TOTAL = 5,
+    VLG_EVAL_CORRECT_OBJ = 6, VLG_EVAL_CORRECT_ATTR = 7, VLG_EVAL_CORRECT_REL = 8, VLG_EVAL_CORRECT_R_REL = 9, VLG_EVAL_TOTAL_OBJ = 10,
+    VLG_EVAL_TOTAL_ATTR = 11, VLG_EVAL_TOTAL_REL = 12, VLG_EVAL_PROCESSED_TOKEN = 13, VLG_EVAL_N_BATCHES = 14,
+    VLG_EVAL_LOSS_SUM = 15 /* the bits of a double */, VLG_EVAL_SLOTS = 16
+};
+size_t vlg_eval_metrics_workspace(int B);
+int vlg_eval_metrics(const int64_t* pred_arc, int ld_pred, const int64_t* gold_arc, const uint8_t* mask, const int64_t* lengths,
+                     const int32_t* factor2img, const int32_t* top5, const float* vis_box, const float* sg_box, const int64_t* sg_type,
+                     const uint8_t* sg_mask, const float* loss, int B, int L, int Q, int R, int add_rel, int add_attr, int add_image,
+                     void* ws, size_t ws_bytes, int64_t* counters, void* stream);
+
 /* ---- Data feed (host code; no device work, no stream).  SURVEY.md section 8 row f4. ----
  *
  * Length bucketing -- ConstantTokenNumSampler.kmeans, src/datamodule/sampler.py:148-191: Lloyd iterations on the sentence
@@ -653,7 +690,7 @@ int vlg_selftest_xlane(int* scratch, void* stream);
 /* Thread-local message for the last non-zero return on this thread ("" if none). */
 const char* vlg_last_error(void);
 
-/* Library / ABI version, e.g. 142 = 0.1.4.2 (145: vlg_step_batch_prepare and vlg_grounding_loss_ntok added; round 6, 142: vlg_attn_fuse / vlg_attn_fuse_backward take key_chunk and a workspace -- the key-split form for the
+/* Library / ABI version, e.g. 142 = 0.1.4.2 (145: vlg_eval_metrics, vlg_eval_metrics_workspace and vlg_deptree_mbr_decode added later under the same number -- no existing argument list changed; 145: vlg_step_batch_prepare and vlg_grounding_loss_ntok added; round 6, 142: vlg_attn_fuse / vlg_attn_fuse_backward take key_chunk and a workspace -- the key-split form for the
  * shipped 1369-key factor layout -- and the gradients' storage type; vlg_attn_fuse_workspace added; round 5, 141: vlg_dropout, vlg_rng_advance, vlg_vis_encoder(_backward) added, vlg_linear_wgrad takes ld_dw and in_dtype;
  * the Python binding refuses a library whose version differs from the one it was written against; round 4: vlg_langfeat_* take the activations' storage type and the SharedDropout masks,
  * vlg_langfeat_rowscale, vlg_ff_* added, vlg_ndmv_potentials* take row strides and the gradients' storage type; round 3, 120: vlg_linear_wgrad, vlg_langfeat_*, vlg_ndmv_potentials*, vlg_dmv1o_viterbi added;

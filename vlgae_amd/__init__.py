@@ -6,6 +6,8 @@ Sub-modules
     langfeat       `lang_feat_max_tree` / `lang_feat_word_only` as fused stages (encoders with SharedDropout masks, arc encoder)
     scorer         score construction feeding the DP (factorised-bilinear scores -> merged potentials)
     parser_ff      the parser's feed-forwards in front of it (head_ff / mid_ff / scorer projections)
+    eval_step      one evaluation step (eval-mode forward, decode, loss, metric update) without a host synchronisation
+    metrics        UAS / UCM, factor -> image and box / relation accuracy as device counters (the reference's metric classes)
     rules1o        the gold tree's rule counts, score and adjoint (the parser's rule-supervised initialisation epochs)
     vis_encoder    the visual encoder's pairwise relation features
     feed           token-budget batch sampler and region-feature collate (host C++)

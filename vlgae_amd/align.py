@@ -525,7 +525,6 @@ def decode_grounding_on_factor(self, inputs, vp):
     Reads the packed features instead of inputs["match_logit"]; returns the same dict: txt_to_factor[b][query][k] =
     (factor name, box id) or ("rel", (box id, box id)) for the five best factors of every unmasked query, and
     txt_to_img[b][query] = the image whose best region matches the query best."""
-    from bisect import bisect_left
     from itertools import accumulate
     txt_feat, txt_mask, _ = inputs["txt_packed"]
     vis_feat, vis_mask, vis_split = inputs["vis_packed"]
@@ -540,8 +539,23 @@ def decode_grounding_on_factor(self, inputs, vp):
     out = grounding_decode(txt_feat, vis_feat, txt_mask, vis_mask, pen, seg, bool(args.use_heuristic), vis_split[0],
                            start[names.index("rel")] if "rel" in names else -1,
                            start[names.index("attr")] if "attr" in names else -1, vp.mask.shape[1] + 1)
-    match = out["top5"][..., :min(5, sum(vis_split))].tolist()         # the one host sync of the decoder, as in :596
-    box_ids = vp.vis_box_index.tolist() if "vis_box_index" in vp else [list(range(200)) for _ in range(len(match))]
+    box_ids = vp.vis_box_index.tolist() if "vis_box_index" in vp else None
+    return grounding_lists(out["top5"], out["factor2img"], txt_mask, names, vis_split, box_ids)
+
+
+def grounding_lists(top5, factor2img, txt_mask, factor_names, vis_split, box_ids=None):
+    """The list half of decode_grounding_on_factor (joint.py:596-629) from the decoder's index tensors top5 [B,Q,5] / factor2img [B,Q]:
+    {"txt_to_factor": [b][kept query][k] = (factor name, box id) or ("rel", (box id, box id)), "txt_to_img": [b][kept query]}, the kept
+    queries being the true rows of txt_mask [B,Q].  box_ids: `vp.vis_box_index` as nested lists (None: the identity).  This is the one
+    place the decoder's output is read on the host (`.tolist()`, as in :596)."""
+    from bisect import bisect_left
+    from itertools import accumulate
+    names = list(factor_names)
+    vis_split = [int(w) for w in vis_split]
+    start = [0] + list(accumulate(vis_split))
+    match = top5[..., :min(5, sum(vis_split))].tolist()                # the one host sync of the decoder, as in :596
+    if box_ids is None:
+        box_ids = [list(range(200)) for _ in range(len(match))]
     processed = []
     for inst_match, box_index in zip(match, box_ids):                  # joint.py:598-622
         inst = []
@@ -558,7 +572,7 @@ def decode_grounding_on_factor(self, inputs, vp):
             inst.append(row)
         processed.append(inst)
     keep = _plain(txt_mask).tolist()
-    return {"txt_to_factor": _filter_list(processed, keep), "txt_to_img": _filter_list(out["factor2img"], keep)}
+    return {"txt_to_factor": _filter_list(processed, keep), "txt_to_img": _filter_list(factor2img, keep)}
 
 
 # ----------------------------------------------------------------------------------------------

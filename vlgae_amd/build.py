@@ -25,9 +25,11 @@ DP_FLAGS = ("-ffinite-math-only",)
 # (input type) -- 12 objects of 8 kernels each instead of one 100-kernel object that took 5.5 minutes on one core.
 DP_INST = tuple(("vlg_dp_inst.hip", f"vlg_dp_inst_{f}{s}{i}", DP_FLAGS + (f"-DVLG_INST_FAMILY={f}", f"-DVLG_INST_SR={s}", f"-DVLG_INST_IN={i}"))
                 for f in (0, 1, 2) for s in (0, 1) for i in (0, 1))
+# the MBR decode (vlg_deptree_mbr_decode): DepTree / Max with the valence sum of the [B,N,N,2] marginals in the load stage
+DP_INST += (("vlg_dp_inst.hip", "vlg_dp_inst_212", DP_FLAGS + ("-DVLG_INST_FAMILY=2", "-DVLG_INST_SR=1", "-DVLG_INST_IN=2")),)
 UNITS = DP_INST + (("vlg_dp.hip", "vlg_dp", DP_FLAGS), ("vlg_dp_pair.hip", "vlg_dp_pair", DP_FLAGS)) + tuple(
     (src, os.path.splitext(src)[0], ()) for src in
-    ("vlg_align.hip", "vlg_attn.hip", "vlg_ground.hip", "vlg_decode.hip", "vlg_arc.hip", "vlg_rel.hip", "vlg_gemm.hip", "vlg_langfeat.hip", "vlg_ff.hip", "vlg_ffgemm.hip", "vlg_encoders.hip", "vlg_scorer.hip", "vlg_batch.hip", "vlg_rules1o.hip", "vlg_feed.cpp", "vlg_capi.cpp"))
+    ("vlg_align.hip", "vlg_attn.hip", "vlg_ground.hip", "vlg_decode.hip", "vlg_arc.hip", "vlg_rel.hip", "vlg_gemm.hip", "vlg_langfeat.hip", "vlg_ff.hip", "vlg_ffgemm.hip", "vlg_encoders.hip", "vlg_scorer.hip", "vlg_batch.hip", "vlg_rules1o.hip", "vlg_eval.hip", "vlg_feed.cpp", "vlg_capi.cpp"))
 SOURCES = tuple(sorted({u[0] for u in UNITS}))
 
 

@@ -22,6 +22,7 @@ namespace vlg {
 VLG_STUB(0, 0, 0, DmvArgs) VLG_STUB(0, 1, 0, DmvArgs) VLG_STUB(0, 1, 1, DmvArgs)
 VLG_STUB(1, 0, 0, RulesArgs) VLG_STUB(1, 0, 1, RulesArgs) VLG_STUB(1, 1, 0, RulesArgs) VLG_STUB(1, 1, 1, RulesArgs)
 VLG_STUB(2, 0, 0, DepArgs) VLG_STUB(2, 0, 1, DepArgs) VLG_STUB(2, 1, 0, DepArgs) VLG_STUB(2, 1, 1, DepArgs)
+VLG_STUB(2, 1, 2, DepArgs)
 #undef VLG_STUB
 }  // namespace vlg
 #endif
@@ -244,6 +245,21 @@ int vlg_deptree_decode(const void* arc, const int64_t* lengths, int B, int N, in
     if (B > 0 && !heads) return vlg::set_error(VLG_ERR_ARG, "deptree_decode: null heads");
     return vlg::run_dep<true>(arc, lengths, B, N, in_dtype, VLG_SR_MAX, nullptr, best_score, nullptr, heads, ws,
                               ws_bytes, stream);
+}
+
+int vlg_deptree_mbr_decode(const float* marginals, const int64_t* lengths, int B, int N, float* best_score, int64_t* heads, void* ws,
+                           size_t ws_bytes, void* stream) {
+    using namespace vlg;
+    if (B < 0 || N < 2) return set_error(VLG_ERR_SHAPE, "deptree_mbr_decode: need B >= 0 and N >= 2 (got B=%d N=%d)", B, N);
+    if (N > 255) return set_error(VLG_ERR_SHAPE, "deptree_mbr_decode: N=%d exceeds the supported maximum of 255", N);
+    if (B == 0) return 0;
+    if (!marginals || !best_score || !heads) return set_error(VLG_ERR_ARG, "deptree_mbr_decode: null buffer");
+    const int mode = pick_mode<DepLayout>(N, true, true, kLdsBudget);
+    const DepLayout L(N, true, true, mode);
+    if (L.ws_bytes * (size_t)B > ws_bytes || (L.ws_bytes && !ws))
+        return set_error(VLG_ERR_WORKSPACE, "deptree_mbr_decode: N=%d needs a %zu-byte workspace (got %zu)", N, L.ws_bytes * (size_t)B, ws_bytes);
+    const DepArgs a{marginals, lengths, B, N, nullptr, best_score, nullptr, heads, ws, L.ws_bytes, L.lds_bytes, (hipStream_t)stream};
+    return VLG_DP_INST_NAME(2, 1, 2)(true, mode == 0 && N <= kShortN ? kModeShort : mode, a);
 }
 
 int vlg_dmv1o_rules(const void* attach_rule, const void* dec, const void* root_rule, int root_per_sentence,

@@ -108,6 +108,14 @@ struct BF16In {
     }
 };
 
+// The MBR decode's load stage (src/model/ldndmv.py:294-299: DependencyCRF(marginals.sum(-1))): the arc score is the sum of the two
+// valence marginals, read from the [N][N][2] fp32 marginals directly -- one element of T per arc, no [N][N] intermediate.  A two-term
+// fp32 sum has one order: the value is the one `marginals.sum(-1)` holds.
+struct ValSumIn {
+    using T = float2;
+    static VLG_HDM float ld(const T* p, size_t i) { const float2 v = p[i]; return v.x + v.y; }
+};
+
 // chart pitch: odd and >= N + 1 so that row-strided (column) walks hit distinct LDS banks
 VLG_HOSTDEV int chart_pitch(int N) { return (N + 1) | 1; }
 

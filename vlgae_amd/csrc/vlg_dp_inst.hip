@@ -1,6 +1,6 @@
 // vlg_dp_inst.hip -- the kernel instantiations of one (family, semiring, input type) of the structured DP.
 // Compiled 12 times by vlgae_amd/build.py with -DVLG_INST_FAMILY={0,1,2} -DVLG_INST_SR={0,1} -DVLG_INST_IN={0,1}
-// (see vlg_dp_kernels.h); each object holds the 2 (inside / fused) x 5 (four placement modes + the short-sentence code image of placement 0) kernels of its combination.
+// (see vlg_dp_kernels.h), and once more for the MBR decode: DepTree / Max on the valence-summed marginals (2, 1, 2); each object holds the 2 (inside / fused) x 5 (four placement modes + the short-sentence code image of placement 0) kernels of its combination.
 #include "vlg_dp_kernels.h"
 
 #if !defined(VLG_INST_FAMILY) || !defined(VLG_INST_SR) || !defined(VLG_INST_IN)
@@ -11,8 +11,10 @@ namespace vlg {
 
 #if VLG_INST_IN == 0
 using InstIn = F32In;
-#else
+#elif VLG_INST_IN == 1
 using InstIn = BF16In;
+#else   // DepTree / Max only (vlg_deptree_mbr_decode)
+using InstIn = ValSumIn;
 #endif
 
 #if VLG_INST_FAMILY == 0

@@ -470,6 +470,7 @@ VLG_DP_DECLARE(0, DmvArgs)
 VLG_DP_DECLARE(1, RulesArgs)
 VLG_DP_DECLARE(2, DepArgs)
 #undef VLG_DP_DECLARE
+int VLG_DP_INST_NAME(2, 1, 2)(bool bwd, int mode, const DepArgs& a);   // DepTree / Max on ValSumIn: arc = [B,N,N,2] fp32 marginals
 
 template <typename K>
 static int prep(K kernel, size_t lds) {

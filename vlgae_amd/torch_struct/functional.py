@@ -226,6 +226,26 @@ def deptree_decode(arc, lengths=None):
     return best, heads
 
 
+def deptree_mbr_decode(marginals, lengths=None):
+    """The MBR decode of src/model/ldndmv.py:294-299 from the DMV1o arc marginals [B,N,N,2] (float32: `grad_attach` of the Log
+    semiring's inside-outside pass): `DependencyCRF(marginals.sum(-1)).argmax` as (best_score [B], heads [B,N] int64) in ONE DepTree
+    launch -- the valence sum is taken in its load stage, no [B,N,N] tensor.  Equals `deptree_decode(marginals.sum(-1))` bit for bit."""
+    _C.require_gpu(marginals, "deptree_mbr_decode")
+    if marginals.dim() != 4 or marginals.shape[1] != marginals.shape[2] or marginals.shape[3] != 2:
+        raise ValueError(f"deptree_mbr_decode: marginals must be [B,N,N,2], got {tuple(marginals.shape)}")
+    if marginals.dtype != torch.float32:
+        raise ValueError(f"deptree_mbr_decode: marginals must be float32 (the DP writes them so), got {marginals.dtype}")
+    B, N = marginals.shape[:2]
+    m = marginals.detach().contiguous()
+    lengths = _lengths(lengths, B, m.device, allow_none=True)
+    best = torch.empty(B, dtype=torch.float32, device=m.device)
+    heads = torch.empty((B, N), dtype=torch.int64, device=m.device)
+    ws, nb = _workspace(_C.OP_DEPTREE_INSIDE_OUTSIDE, B, N, _C.SEMIRING_MAX, m.device)
+    _C.check(_C.lib().vlg_deptree_mbr_decode(_C.ptr(m), _C.ptr(lengths), B, N, _C.ptr(best), _C.ptr(heads), _C.ptr(ws), nb,
+                                             _C.stream_of(m)), "deptree_mbr_decode")
+    return best, heads
+
+
 def dmv1o_rules_run(attach_rule, dec, root_rule, token, lengths, semiring, want_grad, head_mask=None, want_heads=False,
                     mask_fill=-1e20, grad_logZ=None):
     """Raw launcher of the rule-table DP (include/vlgae_amd.h: vlg_dmv1o_rules).
