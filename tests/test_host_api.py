@@ -122,6 +122,42 @@ def test_bench_train_shapes_match_the_step_and_parser_ff_names():
     assert 6.3e6 < n_model < 7.5e6, n_model
 
 
+def test_train_and_eval_steps_hold_the_same_model():
+    """For the object-only and the shipped factor layout: train_step.build and eval_step.build with the same seed hold the same
+    parameters and the same synthetic batch, bit for bit, and that model is step_model.param_table's: names, shapes, storage types,
+    readiness groups -- also what the dry-run stand-in of the sharded step (bench.sharded_step._param_shapes) lists.  Both builders
+    construct on the CPU; no step is run."""
+    from vlgae_amd import eval_step, step_model, train_step
+    from vlgae_amd.bench import sharded_step as bench_train
+    cpu = torch.device("cpu")
+    W = dict(d=16, h=24, E=40, Et=8, T=11, H=16, nb=6, r=4, n_vis=32)
+    B, L, R, dtype, ff_dtype = 3, 5, 4, torch.bfloat16, torch.float32
+    for factors in ((), ("rel", "attr", "img")):
+        kw = dict(seed=5, dtype=dtype, ff_dtype=ff_dtype, factors=factors, **W)
+        train, ev = train_step.build(B, L, R, cpu, **kw), eval_step.build(B, L, R, cpu, **kw)
+        assert list(train.P) == list(ev.P)
+        for k in train.P:
+            assert train.P[k].dtype == ev.P[k].dtype and torch.equal(train.P[k], ev.P[k]), k
+            assert not ev.P[k].requires_grad and train.P[k].requires_grad == (k != "vis_box_feat"), k
+        assert torch.equal(train.lengths, ev.lengths)
+        for k in ("token", "tag", "box_mask"):
+            assert torch.equal(train.batch[k], ev.batch[k]), k
+        n_enc = 1 + ("rel" in factors) + ("attr" in factors)
+        table = step_model.param_table(n_enc=n_enc, B=B, L=L, R=R, **W)
+        types = dict(dtype=dtype, ff_dtype=ff_dtype, float32=torch.float32)
+        assert [(k, tuple(t.shape), t.dtype) for k, t in train.P.items()] == [(k, tuple(s), types[c]) for k, s, c, _ in table]
+        assert [k for k, _, _, _ in table][:13] == ["emb", "vis_box_feat", "w_text", "w_venc", "b_venc", "w_vis", "w_enc", "b_enc", "ln_w", "ln_b", "w1", "w2", "b"]
+        assert [k for k, _, _, _ in table][-3:] == ["token_emb", "root_emb", "dec_emb"]
+        assert train.ready_groups == step_model.ready_groups(train.names)
+        assert sorted(k for g in train.ready_groups for k in g) == sorted(train.trainable)
+        # the dry-run stand-in of the sharded step reads the same table, at the shipped widths
+        f = bench_train.FF_SHAPES
+        shapes, groups = bench_train._param_shapes(n_enc=n_enc)
+        shipped = step_model.param_table(d=128, n_vis=bench_train.N_VIS, n_enc=n_enc, **f)
+        assert shapes == {k: s for k, s, _, _ in shipped if k not in ("emb", "vis_box_feat")}
+        assert sorted(shapes) == sorted(train.trainable) and groups == step_model.ready_groups(sorted(shapes)) == train.ready_groups
+
+
 def test_parser_ff_refuses_unsupported_widths():
     """n_mid != hidden_size or unequal scorer ranks are valid reference configurations that the fused pass does not cover --
     it must refuse them by shape (no GPU needed: the check runs before any kernel)."""

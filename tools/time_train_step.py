@@ -1,5 +1,5 @@
 """Eager vs HIP-graph timing of the training step (vlgae_amd/train_step.py) + host-side profile.
-    python tools/time_train_step.py [B L R] [--f32] [--r3] [--shipped: factors rel attr img, i.e. 1369 columns at R = 36] [--profile]
+    python tools/time_train_step.py [B L R] [--f32] [--shipped: factors rel attr img, i.e. 1369 columns at R = 36] [--profile]
                                     [--dep-loss=viterbi|gold_rules|partition: the parser's loss (gold_rules: a random gold tree per sentence)]"""
 import sys, time, torch
 sys.path.insert(0, '.'); sys.path.insert(0, 'tools')
@@ -22,7 +22,7 @@ if dep_loss == 'gold_rules':   # the batch's gold trees: one root, every other w
             arc[b, order[i]] = order[int(torch.randint(0, i, (1,), generator=g))] + 1
     kw['given'] = dict(lengths=lengths, arc=arc)
 print('dep_loss', dep_loss)
-step = train_step.build(B, L, V, dev, wiring='r3' if '--r3' in sys.argv else 'reference', dtype=torch.float32 if '--f32' in sys.argv else torch.bfloat16, **kw)
+step = train_step.build(B, L, V, dev, dtype=torch.float32 if '--f32' in sys.argv else torch.bfloat16, **kw)
 for _ in range(5): res = step()
 torch.cuda.synchronize()
 import hashlib

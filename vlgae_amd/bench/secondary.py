@@ -435,13 +435,12 @@ def round3_entries(B, L, dtype, dev, g):
     return res
 
 
-def train_step_entry(B, L, V, dtype, dev, wiring="reference", factors=()):
+def train_step_entry(B, L, V, dtype, dev, factors=()):
     """configs[4]: vlgae_amd.train_step.build -- the function tests/test_gpu_parity.py::test_training_step_reference_wiring pins on
     fixtures made by the reference's own methods, from the frozen features to every trainable gradient -- eager and as one captured
-    HIP graph.  factors: the visual factors beside the objects (the shipped model: rel, attr, img = 1369 columns at 36 regions).
-    wiring="r3": round 3's chain (bench continuity only; it is not what the reference wires)."""
+    HIP graph.  factors: the visual factors beside the objects (the shipped model: rel, attr, img = 1369 columns at 36 regions)."""
     from vlgae_amd import train_step
-    step = train_step.build(B, L, V, dev, dtype=dtype, wiring=wiring, factors=factors)
+    step = train_step.build(B, L, V, dev, dtype=dtype, factors=factors)
     for _ in range(5):
         step()
 
@@ -454,20 +453,15 @@ def train_step_entry(B, L, V, dtype, dev, wiring="reference", factors=()):
         torch.cuda.synchronize(dev)
         return (time.perf_counter() - t0) / n * 1e3, (t1 - t0) / n * 1e3
     eager_ms, enqueue_ms = wall(step, 30)
-    if wiring == "reference":
-        what = ("one training step as the reference wires it (base.py:215-241, joint.py:658-711, ldndmv.py:171-216,260-285, fn.py:50-56), from "
-                "the FROZEN features: VisBoxRelSimpleEncoder (box_fc" + ("".join(f" | {f}_fc" for f in factors if f != "img")) + " on [box ; mean box], 2048-d "
-                "region features) + MLPEncoder (nn.Dropout p=0.33 drawn per step + Linear 800->256) -> vis_mlp_pre_matching -> lang_feat_word_only -> attention fuse -> [fused x] context mean + the parser's feed-forwards "
-                "(vlgae_amd.parser_ff: head_ff / mid_ff / scorer projections, E=800 H=256 n_bottleneck=150 r=16, their dropout 0.33 / 0.3 drawn per step) -> score construction -> "
-                "[un-fused x] lang_feat_max_tree (DMV1o marginals || one Viterbi pass, word|child|parent encoders with SharedDropout p=0.33 "
-                "drawn per step, arc encoder) -> alignment maxima with the POS prior + grounding cross-entropies (ragged vis_mask) -> "
-                "-DMV1o.max -> 0.5 mt + 0.5 dep -> / num_token -> gradients to every input feature and parameter")
-    else:
-        what = ("ROUND 3's chain (not the reference's wiring: fused x into lang_feat_max_tree, scorer inputs / vis_feat / fuse word "
-                "features as leaves, no prior / dropout / alpha): score construction -> attention_fuse -> lang_feat_max_tree -> "
-                "grounding loss -> -DMV1o.max -> gradients")
-    res = {"eager_ms": eager_ms, "host_enqueue_ms": enqueue_ms, "wiring": wiring,
-           "what": what + f" (vlgae_amd/train_step.py), B={B} L={L} R={V} regions, {getattr(step, 'shape', {}).get('V', V)} factor columns, d=128 h=256, "
+    what = ("one training step as the reference wires it (base.py:215-241, joint.py:658-711, ldndmv.py:171-216,260-285, fn.py:50-56), from "
+            "the FROZEN features: VisBoxRelSimpleEncoder (box_fc" + ("".join(f" | {f}_fc" for f in factors if f != "img")) + " on [box ; mean box], 2048-d "
+            "region features) + MLPEncoder (nn.Dropout p=0.33 drawn per step + Linear 800->256) -> vis_mlp_pre_matching -> lang_feat_word_only -> attention fuse -> [fused x] context mean + the parser's feed-forwards "
+            "(vlgae_amd.parser_ff: head_ff / mid_ff / scorer projections, E=800 H=256 n_bottleneck=150 r=16, their dropout 0.33 / 0.3 drawn per step) -> score construction -> "
+            "[un-fused x] lang_feat_max_tree (DMV1o marginals || one Viterbi pass, word|child|parent encoders with SharedDropout p=0.33 "
+            "drawn per step, arc encoder) -> alignment maxima with the POS prior + grounding cross-entropies (ragged vis_mask) -> "
+            "-DMV1o.max -> 0.5 mt + 0.5 dep -> / num_token -> gradients to every input feature and parameter")
+    res = {"eager_ms": eager_ms, "host_enqueue_ms": enqueue_ms, "wiring": "reference",
+           "what": what + f" (vlgae_amd/train_step.py), B={B} L={L} R={V} regions, {step.shape['V']} factor columns, d=128 h=256, "
                           "synthetic frozen features: random 800-d embeddings / 2048-d region features (BERT / Faster-RCNN weights are not in the container)",
            "sentences_per_s_eager": B / (eager_ms * 1e-3)}
     gr = torch.cuda.CUDAGraph()
@@ -485,7 +479,7 @@ def train_step_entry(B, L, V, dtype, dev, wiring="reference", factors=()):
     res.update(graph_ms=graph_ms, sentences_per_s_graph=B / (graph_ms * 1e-3),
                note="graph replay has no host work between kernels: graph_ms is the device time of the chain; "
                     "eager_ms - graph_ms is what the Python / autograd host path still costs")
-    if wiring == "reference" and not factors and dtype != torch.float32:
+    if not factors and dtype != torch.float32:
         del gr, step
         try:   # the same step in float32 (the reference's `precision: 32`, config/trainer/train.yaml:20): split-K weight gradients on three bf16 products,
             # arc trilinear and arg-max alignment on two fp16 parts per operand (three MFMAs per product; float32-level results)
@@ -502,11 +496,6 @@ def train_step_entry(B, L, V, dtype, dev, wiring="reference", factors=()):
             res["parser_feed_forward"] = parser_ff_ms(B, L, dtype, dev)
         except Exception as e:
             res["parser_feed_forward"] = {"error": repr(e)[:200]}
-        try:
-            c = train_step_entry(B, L, V, dtype, dev, wiring="r3")
-            res["round3_chain"] = {"graph_ms": c["graph_ms"], "eager_ms": c["eager_ms"], "what": c["what"]}
-        except Exception as e:
-            res["round3_chain"] = {"error": repr(e)[:200]}
     return res
 
 

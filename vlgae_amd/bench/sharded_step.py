@@ -27,27 +27,12 @@ MODEL_VIS_ENCODERS = 3                                              # box_fc, re
 
 
 def _param_shapes(d=128, h=256, n_enc=1):
-    """name -> shape of every trainable leaf of train_step.build(wiring="reference") with n_enc visual-encoder MLPs on the path, and the
-    readiness groups (no GPU needed)."""
-    f = FF_SHAPES
-    shapes = dict(b=(d,), b_enc=(3 * d,), ln_b=(h,), ln_w=(h,), w1=(d, d, d), w2=(d, d), w_enc=(3 * d, h), w_vis=(d, h),
-                  w_text=(h, f["E"]), w_venc=(n_enc * h, 2 * N_VIS), b_venc=(n_enc * h,),
-                  token_emb=(f["T"], f["Et"]), root_emb=(1, 10), dec_emb=(2, 10))
-
-    def lin(name, n_in, n_out):
-        shapes[name + ".weight"], shapes[name + ".bias"] = (n_out, n_in), (n_out,)
-    for name, n_in in (("head_ff", f["E"] + f["h"]), ("child_ff", f["Et"]), ("root_ff", 10), ("dec_ff", 10)):
-        lin(f"ff.{name}.linear", n_in, f["H"])
-    for name in ("HASCHILD_linear", "NOCHILD_linear", "LEFT_linear", "RIGHT_linear"):
-        lin(f"ff.mid_ff.{name}.0", f["H"], f["nb"])
-        lin(f"ff.mid_ff.{name}.1", f["nb"], f["H"])
-    for name in ("valence_linear", "direction_linear", "linear1", "linear2"):
-        lin(f"ff.mid_ff.{name}", f["H"], f["H"])
-    for name in ("attach_scorer", "dec_scorer", "root_scorer"):
-        lin(f"ff.{name}.project1", f["H"], f["r"])
-        lin(f"ff.{name}.project2", f["H"], f["r"])
-    ff_names = sorted(k for k in shapes if k.startswith("ff.") or k in ("token_emb", "root_emb", "dec_emb"))
-    return shapes, (["w1", "w2", "b"], ff_names, ["ln_w", "ln_b", "w_enc", "b_enc", "w_vis"], ["w_text", "w_venc", "b_venc"])
+    """name -> shape of every trainable leaf of train_step.build with n_enc visual-encoder MLPs on the path, and the readiness groups:
+    step_model's table at the shipped widths (no GPU needed)."""
+    from vlgae_amd import step_model
+    rows = step_model.param_table(d=d, h=h, n_vis=N_VIS, n_enc=n_enc, **{k: v for k, v in FF_SHAPES.items() if k != "h"})
+    shapes = {name: shape for name, shape, _, _ in rows if name not in ("emb", "vis_box_feat")}
+    return shapes, step_model.ready_groups(sorted(shapes))
 
 
 class _DryStep:

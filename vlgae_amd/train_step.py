@@ -47,14 +47,13 @@ Leaves: the frozen features `emb` [B,L,E] (= what `self.embedding` emits: [BERT 
 tag embedding is trainable) and `vis_box_feat` [B,R,n] (no gradient unless `feature_grads`), and every trainable tensor: `w_text`
 (MLPEncoder.linear), `w_venc` / `b_venc` (the visual encoder's box_fc | rel_fc | attr_fc stacked), `w_vis`, `w_enc` / `b_enc` (word | child |
 parent encoders stacked), `ln_w` / `ln_b`, `w1` / `w2` / `b` (arc encoder), `token_emb` / `root_emb` / `dec_emb` and the "ff.*" feed-forwards.
-
-`wiring="r3"` keeps round 3's chain for continuity of the bench history (fused x fed to lang_feat_max_tree, scorer inputs and
-matching-space features as leaves, plain sum of the two losses): NOT what the reference does; see HISTORY.md section 5.
 """
 import torch
 import torch.nn.functional as F
 
-SLOPE = 0.01           # nn.LeakyReLU() default, nn/common.py:31
+from . import step_model
+from .step_model import SLOPE, init_feed_forward   # noqa: F401 -- (init_feed_forward: re-exported, callers import it from here)
+
 DEP_LOSSES = ("viterbi", "gold_rules", "partition")
 FF_MODULES = ("head_ff", "child_ff", "root_ff", "dec_ff", "mid_ff", "attach_scorer", "dec_scorer", "root_scorer")
 
@@ -120,34 +119,6 @@ def scorer_feed_forward(P, emb, x_fused, drop_head=None, drop_small=None, drop_m
     return x1, x2, y1, y2, root_rule
 
 
-def init_feed_forward(g, dev, dtype, E, h, Et, T, H, nb, r):
-    """Random parameters with the reference modules' shapes (vlgae.yaml: H = 256, n_bottleneck = 150, ranks 16)."""
-    P = {}
-
-    def lin(name, n_in, n_out, bias=True):
-        P[name + ".weight"] = (torch.randn(n_out, n_in, generator=g) * n_in ** -0.5).to(dev, dtype).requires_grad_(True)
-        if bias:
-            P[name + ".bias"] = (torch.randn(n_out, generator=g) * 0.1).to(dev, dtype).requires_grad_(True)
-
-    for name, n_in in (("head_ff", E + h), ("child_ff", Et), ("root_ff", 10), ("dec_ff", 10)):
-        lin(f"ff.{name}.linear", n_in, H)
-    for name in ("HASCHILD_linear", "NOCHILD_linear", "LEFT_linear", "RIGHT_linear"):
-        if nb:
-            lin(f"ff.mid_ff.{name}.0", H, nb)
-            lin(f"ff.mid_ff.{name}.1", nb, H)
-        else:
-            lin(f"ff.mid_ff.{name}", H, H)
-    for name in ("valence_linear", "direction_linear", "linear1", "linear2"):
-        lin(f"ff.mid_ff.{name}", H, H)
-    for name in ("attach_scorer", "dec_scorer", "root_scorer"):
-        lin(f"ff.{name}.project1", H, r)
-        lin(f"ff.{name}.project2", H, r)
-    P["token_emb"] = torch.randn(T, Et, generator=g).to(dev, dtype).requires_grad_(True)
-    P["root_emb"] = torch.randn(1, 10, generator=g).to(dev, dtype).requires_grad_(True)
-    P["dec_emb"] = torch.randn(2, 10, generator=g).to(dev, dtype).requires_grad_(True)
-    return P
-
-
 def forced_tree_score(md, ma, heads, lengths, big=1e4):
     """Score of the dependency tree `heads` [B,N] (heads[b,c] = head of word c, 0 = the root token) under root-merged DMV1o potentials
     md [B,N,2,2,2] / ma [B,N,N,2 (head, child, valence)]: [B,1], differentiable w.r.t. both (its gradient is the tree's derivation
@@ -170,7 +141,7 @@ def forced_tree_score(md, ma, heads, lengths, big=1e4):
 
 
 # ----------------------------------------------------------------------------------------------------------------------------
-def build(B, L, R, dev, dtype=torch.bfloat16, d=128, h=256, seed=11, with_scorer=True, T=45, r=16, wiring="reference", given=None,
+def build(B, L, R, dev, dtype=torch.bfloat16, d=128, h=256, seed=11, T=45, r=16, given=None,
           alpha=0.5, use_pos_prior=True, vis2txt=1.0, p_drop=0.33, E=800, Et=32, H=256, nb=150, p_ff_drop=0.33, p_mid_drop=0.3,
           factors=(), n_vis=2048, p_enc=0.33, pos_for=None, ln_eps=1e-5, ff_dtype=None, fused_ff=True, feature_grads=False, rng=None,
           batch_on_device=False, dep_loss="viterbi"):
@@ -206,9 +177,7 @@ def build(B, L, R, dev, dtype=torch.bfloat16, d=128, h=256, seed=11, with_scorer
     `forced_heads` only changes the tree it reads.  "partition": the marginal loss (viterbi_training: false), -logZ of the step's
     potentials, reusing lang_feat_max_tree's inside-outside pass.  Every mode seeds its per-sentence score with the same coefficient
     -(1 - alpha) / num_token; step.last["dep_score"] holds it.
-    Returns step(); step() -> (loss, {name: gradient}, ()).
-
-    wiring="r3": round 3's chain (see the module docstring); `with_scorer` only matters there, and R is its V."""
+    Returns step(); step() -> (loss, {name: gradient}, ())."""
     if dep_loss not in DEP_LOSSES:
         raise ValueError(f"train_step.build: dep_loss {dep_loss!r} (one of {DEP_LOSSES})")
     has_arc = bool(given) and "arc" in given
@@ -216,63 +185,15 @@ def build(B, L, R, dev, dtype=torch.bfloat16, d=128, h=256, seed=11, with_scorer
         raise ValueError("train_step.build(dep_loss='gold_rules') needs the batch's gold trees: given['arc'] [B,L] int64 (1-based heads, 0 = root)")
     if has_arc and dep_loss != "gold_rules":
         raise ValueError(f"train_step.build: given['arc'] is only read with dep_loss='gold_rules' (got dep_loss={dep_loss!r})")
-    if wiring == "r3" and dep_loss != "viterbi":
-        raise ValueError("train_step.build: wiring='r3' has the Viterbi loss only")
-    if wiring == "r3":
-        return _build_r3(B, L, R, dev, dtype, d, h, seed, with_scorer, T, r)
-    if wiring != "reference":
-        raise ValueError(wiring)
     import vlgae_amd.torch_struct as ts
-    from vlgae_amd import align, encoders, langfeat, parser_ff, rules1o, scorer
-    N, Q = L + 1, 2 * (L + 1)
-    given = dict(given or {})
-    given_ptrs = {k: t.data_ptr() for k, t in given.items() if torch.is_tensor(t)}
-    factors = tuple(factors)
-    if any(f not in ("rel", "attr", "img") for f in factors):
-        raise ValueError(f"train_step.build: factors {factors}")
-    add_rel, add_attr, add_image = "rel" in factors, "attr" in factors, "img" in factors
-    _, V, vis_split, factor_names = encoders.factor_layout(R, add_rel, add_attr, add_image)
-    n_enc = 1 + add_rel + add_attr
+    from vlgae_amd import align, encoders, langfeat, rules1o
+    Q = 2 * (L + 1)
+    given_as_it_came, given = given or {}, dict(given or {})
     ff_dtype = dtype if ff_dtype is None else ff_dtype
-    g = torch.Generator().manual_seed(seed)
-    rnd = lambda *s, sc=1.0: torch.randn(*s, generator=g) * sc
-
-    def leaf(name, make, dt=dtype, grad=True):
-        t = given.pop(name) if name in given else make()
-        return t.detach().to(dev, dt).contiguous().requires_grad_(grad)
-
-    # ---- the frozen features (BERT subword + tag embedding; Faster-RCNN region features) and every trainable weight behind them ----
-    P = dict(
-        emb=leaf("emb", lambda: rnd(B, L, E, sc=0.5), ff_dtype), vis_box_feat=leaf("vis_box_feat", lambda: rnd(B, R, n_vis, sc=0.5), grad=feature_grads),
-        w_text=leaf("w_text", lambda: rnd(h, E, sc=E ** -0.5), ff_dtype),
-        w_venc=leaf("w_venc", lambda: rnd(n_enc * h, 2 * n_vis, sc=(2 * n_vis) ** -0.5)), b_venc=leaf("b_venc", lambda: rnd(n_enc * h, sc=0.1)),
-        w_vis=leaf("w_vis", lambda: rnd(d, h, sc=h ** -0.5)),
-        w_enc=leaf("w_enc", lambda: rnd(3 * d, h, sc=h ** -0.5)), b_enc=leaf("b_enc", lambda: rnd(3 * d, sc=0.1)),
-        ln_w=leaf("ln_w", lambda: torch.ones(h), torch.float32), ln_b=leaf("ln_b", lambda: torch.zeros(h), torch.float32),
-        w1=leaf("w1", lambda: rnd(d, d, d, sc=1.0 / d)), w2=leaf("w2", lambda: rnd(d, d, sc=d ** -0.5)), b=leaf("b", lambda: rnd(d, sc=0.1)),
-    )
-    ff_given = {k: given.pop(k) for k in list(given) if k.startswith("ff.") or k in ("token_emb", "root_emb", "dec_emb")}
-    if ff_given:
-        P.update({k: t.detach().to(dev, ff_dtype).contiguous().requires_grad_(True) for k, t in ff_given.items()})
-    else:
-        P.update(init_feed_forward(g, dev, ff_dtype, E, h, Et, T, H, nb, r))
-    # ---- the batch ----
-    if "lengths" in given:
-        lengths = given.pop("lengths").to(dev, torch.int64)
-    else:
-        lengths = torch.randint(max(1, L // 2), L + 1, (B,), generator=g)
-        lengths[0] = L
-        lengths = lengths.to(dev)
-    token = given.pop("token").to(dev) if "token" in given else torch.randint(0, P["token_emb"].shape[0], (B, L), generator=g).to(dev)
-    tag = given.pop("tag").to(dev) if "tag" in given else torch.randint(0, 7, (B, L), generator=g).to(dev)
-    if "box_mask" in given:
-        box_mask = given.pop("box_mask").to(dev, torch.bool)
-    else:   # ragged region lists as the reference's collate builds them: image i has n_i <= R boxes, `masks_output[i, :n_i] = True` and
-        # padding behind them (src/datamodule/task/vlparse.py:68-83) -- a PREFIX mask per image, n_i drawn from [0.6 R, R]
-        n_box = torch.randint(max(1, (3 * R) // 5), R + 1, (B,), generator=g)
-        box_mask = (torch.arange(R)[None] < n_box[:, None]).to(dev)
-    if not batch_on_device:
-        vmask = encoders.factor_mask(box_mask, add_rel, add_attr, add_image)   # vis_feat_unprune's mask (joint.py:140-170): data, built once per batch
+    P, batch, layout, _ = step_model.build_inputs("train_step.build", given, seed, B, L, R, dev, dtype, ff_dtype, d, h, E, Et, T, H, nb, r, n_vis,
+                                                  factors, train=True, feature_grads=feature_grads)
+    lengths, token, tag, box_mask = batch["lengths"], batch["token"], batch["tag"], batch["box_mask"]
+    factors, V, vis_split, factor_names = layout["factors"], layout["V"], layout["vis_split"], layout["factor_names"]
     fixed_drop = given.pop("drop") if "drop" in given else "draw"
     if fixed_drop is not None and not isinstance(fixed_drop, str):
         fixed_drop = fixed_drop.to(dev, torch.float32).permute(1, 0, 2).contiguous()      # [B,4,d]
@@ -286,34 +207,22 @@ def build(B, L, R, dev, dtype=torch.bfloat16, d=128, h=256, seed=11, with_scorer
     if given:
         raise ValueError(f"train_step.build: unknown given entries {sorted(given)}")
     if batch_on_device:
-        # a given tensor the step had to copy (another dtype / device, not contiguous) would keep its build-time values for ever: later
-        # batches copied into it and optimiser updates would be ignored without a word -- refuse it
-        used = dict(P, lengths=lengths, token=token, tag=tag, box_mask=box_mask, **({} if arc is None else dict(arc=arc)))
-        copied = [k for k, p in given_ptrs.items() if k in used and used[k].data_ptr() != p]
-        if copied:
-            raise ValueError(f"train_step.build(batch_on_device=True): given {copied} would be copied, not used in place -- pass them "
-                             f"on {dev}, contiguous, in the step's types (parameters: `dtype`, ln_w / ln_b float32, emb / w_text / token_emb / "
-                             "root_emb / dec_emb / ff.*: `ff_dtype`; lengths / token / tag / arc int64; box_mask bool)")
+        step_model.check_in_place("train_step.build(batch_on_device=True)", given_as_it_came, dict(P, **batch, **({} if arc is None else dict(arc=arc))),
+                                  dev, dict(int64=("arc",)))
     if rng is None:
         rng = encoders.DeviceRng(seed * 7919 + 17, dev)   # the counter-based dropout draws of the step (advanced on the device once per step)
-    if pos_for is None:
-        pos_for = dict(obj=torch.tensor([0, 1, 2]), rel=torch.tensor([2, 3]), attr=torch.tensor([4]))
-    pos_for = {k: t.to(dev) for k, t in pos_for.items()}
+    pos_for = step_model.default_pos_for(pos_for, dev)
     names = sorted(k for k in P if P[k].requires_grad)
     leaves = [P[k] for k in names]
     aux = {}
     if batch_on_device:
-        # buffers the first launch of every step fills from the batch tensors' current contents (vlg_step_batch_prepare)
-        pos_for = {k: t.to(torch.int64).contiguous() for k, t in pos_for.items()}
-        lengths, tag = lengths.contiguous(), tag.contiguous()
-        vmask = torch.empty((B, V), dtype=torch.bool, device=dev)
-        pen = torch.empty((B, Q, len(vis_split)), dtype=torch.float32, device=dev) if use_pos_prior else None
-        seg = align.segment_map(vis_split, dev) if use_pos_prior else None      # a function of the layout alone
-        num_token = num_token_f = torch.empty((), dtype=torch.float32, device=dev)   # read by the grounding loss's kernel
-        coef = torch.empty(2, dtype=torch.float32, device=dev)
+        buf = step_model.batch_buffers(B, Q, layout, pos_for, use_pos_prior, dev)
+        vmask, pen, seg, coef, seed_max, pos_for = buf["vmask"], buf["pen"], buf["seg"], buf["coef"], buf["seed"], buf["pos_for"]
+        num_token = num_token_f = buf["num_token"]
         c_mt = coef[0]
-        seed_max = torch.empty(B, dtype=torch.float32, device=dev)
     else:
+        # vis_feat_unprune's mask (joint.py:140-170): data, built once per batch
+        vmask = encoders.factor_mask(box_mask, layout["add_rel"], layout["add_attr"], layout["add_image"])
         num_token = lengths.sum()                                     # a 0-d tensor like vp.num_token (var_pool.py:18)
         num_token_f = float(num_token.item())
         # the POS prior table (joint.py:446-470) is a function of the batch's tags only -- data, like the masks: built once per batch
@@ -353,30 +262,9 @@ def build(B, L, R, dev, dtype=torch.bfloat16, d=128, h=256, seed=11, with_scorer
             align.step_batch_prepare(lengths, tag, box_mask, factors, pos_for, Q, alpha, vmask, pen, num_token, coef, seed_max)
         drop, ff_masks = draw_masks()
         d0, d3 = (None, None) if drop is None else (drop[:, 0:1], drop[:, 1:4])
-        # ---- JointModelBase.forward, base.py:229 / :68: the two trainable encoders on the frozen features ----
-        vis_mid, _, _ = encoders.vis_box_rel_encoder(P["vis_box_feat"], P["w_venc"], P["b_venc"], add_rel, add_attr, add_image, SLOPE)
-        if enc_drop is None or p_enc == 0:
-            enc_x = encoders.mlp_encoder(P["emb"], P["w_text"], training=False)
-        elif isinstance(enc_drop, str):
-            enc_x = encoders.mlp_encoder(P["emb"], P["w_text"], p_enc, rng=rng)
-        else:
-            enc_x = encoders.mlp_encoder(P["emb"], P["w_text"], p_enc, mask=enc_drop)
-        if enc_x.dtype != dtype:                                          # (ff_dtype != dtype: the language side runs in `dtype`)
-            enc_x = enc_x.to(dtype)
-        # ---- DependencyBoxRel._forward, joint.py:658-675 ----
-        vis_feat = align.linear(vis_mid, P["w_vis"])                                                         # :175 (and again :688: same values)
-        # the word | child | parent encoders' Linear on cat([masked mean, x]) ONCE: joint.py:204-209 (word-only) and :262-273 (max-tree) read the
-        # same un-fused encodings through the same word encoder, under two SharedDropout masks
-        pre = langfeat.encoder_projection(enc_x, lengths, P["w_enc"], P["b_enc"])
-        word0, _, _ = langfeat.lang_feat_word_only(None, lengths, drop=d0, pre=pre, masks=False)             # :667 (the fuse reads the features only)
-        x_f = align.attention_fuse(vis_feat, word0, vis_mid, enc_x, P["ln_w"], P["ln_b"], ln_eps)             # :670-674
-        # ---- DiscriminativeNDMV._forward on the fused copy, ldndmv.py:171-216 ----
-        if fused_ff:   # the same mathematics with folded / fused GEMMs and a hand-written adjoint
-            x1, x2, y1, y2, root_rule = parser_ff.parser_feed_forward(P, P["emb"], x_f, **ff_masks)
-        else:          # module by module, as the reference runs it (explicit masks: the comparison form of the tests)
-            mid = None if p_mid_drop <= 0 else encoders.dropout(torch.ones(4 * (B * L + T_ + 3), H_, device=dev), p_mid_drop, rng=rng, site=encoders.SITE_MID_FF)
-            x1, x2, y1, y2, root_rule = scorer_feed_forward(P, P["emb"], x_f, ff_masks.get("drop_head"), ff_masks.get("drop_small"), mid)
-        md, ma = scorer.ndmv_potentials(x1, x2, y1, y2, root_rule, token)
+        # ---- JointModelBase.forward, DependencyBoxRel._forward, DiscriminativeNDMV._forward: the forward the evaluation step shares ----
+        vis_mid, enc_x, vis_feat, pre, x_f, md, ma = step_model.forward(P, batch, layout, dtype, ln_eps, d0=d0, enc_drop=enc_drop, p_enc=p_enc, rng=rng,
+                                                                        ff_masks=ff_masks, fused_ff=fused_ff)
         # ---- DependencyBoxRel._vis_forward, joint.py:677-691: the UN-fused x; the potentials are constants of this stage (:252-253) ----
         txt, tmask, tmarg = langfeat.lang_feat_max_tree(None, lengths, md.detach(), ma.detach(), None, None, P["w1"],
                                                         P["w2"], P["b"], keep_viterbi=dep_loss == "viterbi", drop=d3, aux=aux, pre=pre,
@@ -404,7 +292,7 @@ def build(B, L, R, dev, dtype=torch.bfloat16, d=128, h=256, seed=11, with_scorer
             viterbi_max=mx if dep_loss == "viterbi" else None, dep_score=mx, mt_loss=mt, heads=aux.get("heads")).items()}
         return loss, dict(zip(names, grads)), ()
 
-    step.names, step.P, step.lengths, step.wiring, step.dep_loss, step.arc = names, P, lengths, wiring, dep_loss, arc
+    step.names, step.P, step.lengths, step.dep_loss, step.arc = names, P, lengths, dep_loss, arc
     # Teacher forcing (parity tests only; None = the reference's behaviour): with a tree given, lang_feat_max_tree reads ITS parents and
     # marginals, and the parser's loss is -score(that tree) instead of -max -- the same function of the parameters the reference
     # differentiates when its own Viterbi tree is that tree (joint.py:256-273 and ldndmv.py:277-281 treat the tree as a constant).  A bf16
@@ -414,74 +302,11 @@ def build(B, L, R, dev, dtype=torch.bfloat16, d=128, h=256, seed=11, with_scorer
                       factors=factors, pos_for=pos_for, use_pos_prior=use_pos_prior, vis2txt=vis2txt, enc_drop=enc_drop, p_enc=p_enc)
     step.shape = dict(B=B, L=L, R=R, V=V, d=d, h=h, E=E, n_vis=n_vis)
     step.trainable = tuple(k for k in names if k not in ("emb", "vis_box_feat"))
-    # Parameters in the order their gradients become FINAL during the backward pass (autograd runs the later-created node first:
-    # -max, grounding loss, lang_feat_max_tree | score construction, the parser's feed-forwards | attention fuse, word-only encoder,
-    # vis_mlp_pre_matching | the text and visual encoders): what a data-parallel trainer's buckets follow.  `step.on_grad(name, grad)`, if set, is called from
-    # inside the backward pass the moment a parameter's (accumulated) gradient exists.
-    ff_names = [k for k in names if k.startswith("ff.") or k in ("token_emb", "root_emb", "dec_emb")]
-    step.ready_groups = (["w1", "w2", "b"], ff_names, ["ln_w", "ln_b", "w_enc", "b_enc", "w_vis"], ["w_text", "w_venc", "b_venc"])
+    # `step.on_grad(name, grad)`, if set, is called from inside the backward pass the moment a parameter's (accumulated) gradient exists;
+    # step.ready_groups is the order in which that happens
+    step.ready_groups = step_model.ready_groups(names)
     step.on_grad = None
     for k in step.trainable:
         P[k].register_hook(lambda g_, k=k: step.on_grad(k, g_) if step.on_grad is not None else None)
     return step
 
-
-# ----------------------------------------------------------------------------------------------------------------------------
-def _build_r3(B, L, V, dev, dtype, d, h, seed, with_scorer, T, r):
-    """Round 3's chain, unchanged (bench continuity only).  Differences from the reference's wiring: the fused x feeds
-    lang_feat_max_tree, the scorers' projected inputs / vis_feat / the fuse's word features are leaves, vis_mask is all-true, no POS
-    prior, no dropout, total = grounding + dep (no alpha, no token reduction)."""
-    import vlgae_amd.torch_struct as ts
-    from vlgae_amd import align, langfeat, scorer
-    N = L + 1
-    g = torch.Generator().manual_seed(seed)
-    rnd = lambda *s, sc=1.0: (torch.randn(*s, generator=g) * sc).to(dev)
-    leaf = lambda *s, sc=1.0, dt=dtype: rnd(*s, sc=sc).to(dt).requires_grad_(True)
-    P = dict(
-        vis_feat=leaf(B, V, d), txt_word=leaf(B, N, d), vis_mid=leaf(B, V, h), enc_x=leaf(B, L, h),
-        ln_w=torch.ones(h, device=dev, requires_grad=True), ln_b=torch.zeros(h, device=dev, requires_grad=True),
-        w_enc=leaf(3 * d, h, sc=h ** -0.5), b_enc=leaf(3 * d, sc=0.1),
-        w1=leaf(d, d, d, sc=1.0 / d), w2=leaf(d, d, sc=d ** -0.5), b=leaf(d, sc=0.1),
-    )
-    dec = torch.randn(B, L, 2, 2, 2, generator=g).log_softmax(-1).to(dev)
-    attach = torch.randn(B, L, L, 2, generator=g).to(dev)
-    root = torch.randn(B, L, generator=g).log_softmax(-1).to(dev)
-    md, ma = ts.DMV1o.merge(dec, attach, root)
-    md, ma = md.to(dtype).contiguous(), ma.to(dtype).contiguous()
-    lengths = torch.randint(max(1, L // 2), L + 1, (B,), generator=g)
-    lengths[0] = L
-    lengths = lengths.to(dev)
-    vmask = torch.ones(B, V, dtype=torch.bool, device=dev)
-    num_token = float(lengths.sum().item())
-    if with_scorer:
-        P.update(sc_x1=leaf(B, L, 2, 2, r, sc=0.5, dt=torch.float32), sc_x2=leaf(T, 2, 2, r, sc=0.5, dt=torch.float32),
-                 sc_y1=leaf(B, L, 2, 2, r, sc=0.5, dt=torch.float32), sc_y2=leaf(2, 2, 2, r, sc=0.5, dt=torch.float32),
-                 sc_root=torch.randn(T, generator=g).log_softmax(-1).to(dev).requires_grad_(True))
-        token = torch.randint(0, T, (B, L), generator=g).to(dev)
-    names = sorted(P)
-    leaves = [P[k] for k in names]
-    pot = [md.detach().requires_grad_(True), ma.detach().requires_grad_(True)]
-    one, minus_one = torch.ones((), device=dev), torch.full((B,), -1.0, device=dev)
-
-    def step(stage_hook=None):
-        x = align.attention_fuse(P["vis_feat"], P["txt_word"], P["vis_mid"], P["enc_x"], P["ln_w"], P["ln_b"], 1e-5)
-        if with_scorer:
-            smd, sma = scorer.ndmv_potentials(P["sc_x1"], P["sc_x2"], P["sc_y1"], P["sc_y2"], P["sc_root"], token)
-            cmd, cma, loss_pot = smd.detach(), sma.detach(), [smd, sma]
-        else:
-            cmd, cma, loss_pot = md, ma, pot
-        txt, tmask, txt_marginal = langfeat.lang_feat_max_tree(x, lengths, cmd, cma, P["w_enc"], P["b_enc"], P["w1"], P["w2"], P["b"],
-                                                               keep_viterbi=True, compute_dtype=dtype)   # (x is the fuse's fp32 output)
-        if stage_hook is not None:
-            txt.register_hook(lambda g_: stage_hook())
-        mt, _ = align.grounding_loss_factor_ce(txt, P["vis_feat"], tmask, vmask, txt_marginal, num_token, 1.0)
-        mx = ts.DMV1o(loss_pot, lengths).max
-        with torch.no_grad():
-            total = mt - mx.sum()
-        # total = mt - sum_b max_b: the two cotangents (+1, -1 per sentence) seed the backward pass directly
-        grads = torch.autograd.grad([mt, mx], leaves + ([] if with_scorer else pot), [one, minus_one.view(mx.shape)])
-        return total, dict(zip(names, grads[:len(names)])), grads[len(names):]
-
-    step.names, step.P, step.lengths, step.wiring = names, P, lengths, "r3"
-    step.trainable = ("b", "b_enc", "ln_b", "ln_w", "w1", "w2", "w_enc")
-    return step
