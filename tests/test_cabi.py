@@ -41,6 +41,11 @@ def test_binding_table_matches_header(lib):
         assert len(params) == len(args), (name, len(params), len(args))
 
 
+def test_native_sources_read_no_environment_variable():
+    csrc = os.path.join(ROOT, "vlgae_amd", "csrc")
+    assert not [f for f in sorted(os.listdir(csrc)) if "getenv" in open(os.path.join(csrc, f)).read()]
+
+
 def test_version_and_error_plumbing(lib):
     from vlgae_amd import _C
     assert lib.vlg_version() >= 100

@@ -11,7 +11,7 @@ from conftest import ROOT
 # kernels on the hot paths bench.py reports (substring of the demangled name)
 HOT = ("dmv1o_kernel<", "dmv1o_rules_kernel<", "deptree_kernel<", "align_max_kernel<", "align_mfma_kernel<", "attn_fuse_mfma_kernel<",
        "attn_fuse_bwd_words_kernel<", "attn_fuse_bwd_regions_kernel<", "tri_kernel<false", "tri_dw2_kernel", "ground_bwd_dense_kernel<",
-       "ground_ce_tile_kernel<", "gemm_tn_kernel", "scorer_fwd_kernel<", "scorer_bwd_kernel<", "langfeat_", "box_rel_", "merge_kernel<",
+       "gemm_tn_kernel", "scorer_fwd_kernel<", "scorer_bwd_kernel<", "langfeat_", "box_rel_", "merge_kernel<",
        "grounding_decode_kernel", "align_bwd_split_kernel<", "align_full_kernel", "tri2_kernel", "align_argmax_kernel<",
        "ground_bwd_ws_kernel<", "ground_ce_tile2_kernel", "align_prior_diag_kernel", "attn_fuse_split_kernel<", "attn_bwd_sweep_kernel<",
        "attn_bwd_combine_kernel<", "attn_fuse_combine_kernel<", "attn_bwd_regions_bf16_kernel<", "ff_gemm_act_kernel", "ff_gemm_act2_kernel",

@@ -1150,12 +1150,14 @@ def test_grounding_loss_golden(oracle_mod, path):
                                         (3, 50, 70, 64, "f32"), (4, 47, 100, 128, "bf16"), (1, 3, 1, 32, "f32"),
                                         (3, 12, 1369, 128, "f32"), (2, 9, 520, 128, "bf16"),
                                         (6, 40, 1369, 128, "bf16"), (7, 30, 1200, 64, "f32"),
-                                        (5, 60, 44, 128, "bf16"), (3, 20, 17, 128, "bf16"), (9, 47, 48, 128, "bf16")])
+                                        (5, 60, 44, 128, "bf16"), (3, 20, 17, 128, "bf16"), (9, 47, 48, 128, "bf16"),
+                                        (3, 3, 4100, 64, "f32")])
 def test_grounding_loss_shapes(oracle_mod, B, L, V, d, dt):
     """Against the fp64 oracle: several row groups (Q > 96 / 48), several region groups (V > 48), one pair, bf16 storage
     (V <= 48: align_argmax_kernel, two passes at Q = 122, odd and full region counts, a batch that is no multiple of eight),
-    and the shipped factor layout's 1369 columns (image-side gradient rows split over several workgroups; caption side with
-    one row per wave and the block-level scan of the scattered terms)."""
+    the shipped factor layout's 1369 columns (image-side gradient rows split over several workgroups; caption side with
+    one row per wave and the block-level scan of the scattered terms), and 4100 columns: eight strips of 513, one more than a block
+    of the LDS-tile cross-entropy has threads, so the streaming cross-entropy kernel (ground_ce_kernel) runs."""
     from vlgae_amd import align
     rng = np.random.default_rng(B * 131 + L * 7 + V)
     Q = 2 * (L + 1)
@@ -1390,8 +1392,7 @@ def test_arc_trilinear_float32_on_fp16_parts(M):
     """float32 operands at X = H = Y = 128 (the reference's `precision: 32`): every MFMA operand row as two fp16 parts under a power-of-two row
     scale, three products per pair (tri3_kernel, tri_dw3_kernel).  Against float64 torch: the error must stay at float32's own level -- 2e-6 of the
     largest entry (the exact-fp32 kernels measured 6e-6 at M = 10 496; two bf16 parts, round 4: 2e-5) -- with rows / cotangents whose magnitudes
-    span 2^24 (every ROW of the row-wise results is held to 1e-5 of its own largest entry: the row scales), bit-reproducible, and equal to the
-    exact-fp32 kernels (VLG_TRI_F32_EXACT, a child process) within the same bound."""
+    span 2^24 (every ROW of the row-wise results is held to 1e-5 of its own largest entry: the row scales), and bit-reproducible."""
     from vlgae_amd import align
     gen = torch.Generator().manual_seed(M)
     rows = torch.exp2(torch.randint(-12, 13, (M, 1), generator=gen).float())             # per-row magnitudes 2^-12 .. 2^12
@@ -3225,6 +3226,35 @@ def test_ff_linear_act_backward_other_contractions(rows, k):
     if k == 512:
         with pytest.raises(RuntimeError):  # a plain layer's adjoint only
             parser_ff._linear_act_bwd(gin, wT, act, out, total=torch.zeros(rows, H, device=dev()))
+
+
+@pytest.mark.parametrize("rows,k", [(77, 32), (333, 512)])
+def test_ff_linear_act_backward_generic_images(rows, k):
+    """Option words outside the compiled set take the generic image of their contraction length (options read at run time): k = 32 with a
+    dropout mask, k = 512 with the accumulate flag (which has nothing to act on without group sums).  Same reference and bounds as the
+    compiled images above."""
+    from vlgae_amd import parser_ff
+    H = 256
+    g = torch.Generator().manual_seed(rows + k)
+    bf = torch.bfloat16
+    gin = torch.randn(rows, k, generator=g).to(dev(), bf)
+    W = (torch.randn(k, H, generator=g) / k ** 0.5).to(dev(), bf)
+    act = torch.randn(rows, H, generator=g).to(dev(), bf)
+    out = torch.full((rows, H), float("nan"), dtype=bf, device=dev())
+    mask, scale = None, 1.0
+    if k == 512:
+        wT = parser_ff._transpose256([W[:H].contiguous(), W[H:].contiguous()], torch.empty(2, H, H, dtype=bf, device=dev()))
+        parser_ff._linear_act_bwd(gin, wT, act, out, accumulate=True)
+    else:
+        mask, scale = (torch.rand(rows, H, generator=g) > 0.3).to(dev(), bf), 1.0 / 0.7
+        parser_ff._linear_act_bwd(gin, W, act, out, w_kn=True, mask=mask, mask_scale=scale)
+    lin = (gin.double() @ W.double()).to(bf)
+    want = torch.empty_like(out)
+    parser_ff._act_bwd(lin, act, want, rows, 1, H, mask=mask, mask_scale=scale)
+    err = (out.double() - want.double()).abs()
+    assert not torch.isnan(out.float()).any()
+    assert float((err / want.double().abs().clamp_min(1.0)).max()) <= 2.0 ** -6 and float(err.mean()) <= 2e-3
+    assert float((err > 2.0 ** -7 * want.double().abs().clamp_min(0.5)).float().mean()) <= 0.02
 
 
 @pytest.mark.parametrize("rows,n,ldw,ldo", [(2048, 800, 864, 800), (10240, 800, 800, 800), (2055, 256, 256, 320), (4100, 40, 48, 40), (3000, 1032, 1032, 1036)])

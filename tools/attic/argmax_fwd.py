@@ -1,5 +1,5 @@
-"""The grounding loss's forward pass alone (arg-max alignment + POS prior + cross-entropies), n calls: the program rocprofv3 is pointed at by
-tools/time_argmax_ablation.sh.   python tools/argmax_fwd.py [masked|unmasked] [shipped]"""
+"""The grounding loss's forward pass alone (arg-max alignment + POS prior + cross-entropies), n calls: a program to point
+rocprofv3 at.   python tools/attic/argmax_fwd.py [masked|unmasked] [shipped]"""
 import sys, torch
 sys.path.insert(0, '.')
 from vlgae_amd import align, encoders

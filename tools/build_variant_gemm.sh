@@ -1,6 +1,7 @@
 #!/bin/bash
 # tools/build_variant_gemm.sh NAME [-Dflags...] -- the built library with vlg_gemm.hip recompiled under extra flags (A/B timing of the split-K weight
 # gradients): tools/variants/lib_NAME.so, selected with VLGAE_AMD_LIB.  Needs a built vlgae_amd/_lib (python -m vlgae_amd.build).
+# Build parameters (numeric): VLG_TN64_STAGE, VLG_TN64_SETS, VLG_TN128_STAGE, VLG_TN128_SETS, VLG_TN_WGS, VLG_TN_BIG_MIN, VLG_SG_U.
 set -e
 cd "$(dirname "$0")/.."
 name=$1; shift

@@ -1,5 +1,6 @@
 #!/bin/bash
-# tools/build_variant_ground.sh NAME [-Dflags...] -- grounding-loss-only library variant (vlg_ground + vlg_align) for A/B timing
+# tools/build_variant_ground.sh NAME [-Dflags...] -- grounding-loss-only library variant (vlg_ground + vlg_align) for A/B timing.
+# Build parameters (numeric): VLG_COOP_BATCHES, VLG_COOP_CAP (vlg_ground.hip), VLG_AF_RT, VLG_AF_WPE (vlg_align.hip).
 set -e
 cd "$(dirname "$0")/.."
 name=$1; shift

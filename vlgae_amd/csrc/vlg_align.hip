@@ -12,7 +12,6 @@
 // A generic fp32-FMA kernel remains for shapes the MFMA path does not take (d > 128 or unaligned d).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include <algorithm>
 #include <type_traits>
@@ -496,14 +495,12 @@ constexpr int kAMThreads = 512, kAMWaves = 8, kAMRows = 48, kAMSlots = kAMRows *
     asm("s_nop 1\n\t" OP " %0, %0, %0 " C "\n\t" OP " %1, %1, %1 " C "\n\t" OP " %2, %2, %2 " C "\n\t" OP " %3, %3, %3 " C \
         : "+v"(m0), "+v"(m1), "+v"(m2), "+v"(m3))
 
-// ARGS (the grounding loss's variant, joint.py:446-483): also records WHERE each maximum sits (first position on ties, like a
-// sequential scan) and, on the diagonal pairs a == b, subtracts the POS prior pen[b,q,seg(v)] before the maxima.  It runs
-// 48-row passes (RT = 3): the position registers would not fit next to 96 rows of caption fragments.
-template <bool ARGS, int RT>
+// RT = row tiles (of 16 queries) per pass.  The maxima only: their positions, which the grounding loss wants, are align_argmax_kernel's.
+template <int RT>
 __global__ __launch_bounds__(kAMThreads, 2) void align_max_kernel(
     const uint16_t* __restrict__ txt, const uint16_t* __restrict__ vis, const uint8_t* __restrict__ tmask,
     const uint8_t* __restrict__ vmask, int B, int A, int Q, int V, float neg_inf, float* __restrict__ out_maxV,
-    float* __restrict__ out_maxQ, int a_per_block, AlignArgs xa) {
+    float* __restrict__ out_maxQ, int a_per_block) {
     constexpr int d = 128, KCH = 4;
     __shared__ uint4 tiles[2][kAMSlots];
     __shared__ uint8_t ckeep_s[2][kAMRows];
@@ -574,14 +571,12 @@ __global__ __launch_bounds__(kAMThreads, 2) void align_max_kernel(
         }
         __syncthreads();
         f32x4 rmx[RT];
-        int rix[ARGS ? RT : 1][4];   // ARGS: column tile that holds the running row maximum (first one on ties: ct ascends)
         auto row_epilogue = [&](int a) {   // row maxima of image a: one 16-lane butterfly per accumulator register
             if (!(b < B && out_maxV)) return;
             const size_t at0 = ((size_t)bc * A + a) * Q + q0 + crow + ccol;
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) {
                 float m0 = rmx[rt][0], m1 = rmx[rt][1], m2 = rmx[rt][2], m3 = rmx[rt][3];
-                const float o0 = m0, o1 = m1, o2 = m2, o3 = m3;
                 VLG_AM_DPP4("v_max_f32_dpp", "quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf");
                 VLG_AM_DPP4("v_max_f32_dpp", "quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf");
                 VLG_AM_DPP4("v_max_f32_dpp", "row_half_mirror row_mask:0xf bank_mask:0xf");
@@ -590,23 +585,6 @@ __global__ __launch_bounds__(kAMThreads, 2) void align_max_kernel(
                 res = is2 ? m2 : res;
                 res = is1 ? m1 : res;
                 res = is0 ? m0 : res;
-                if (ARGS) {
-                    // where: the smallest region index among the lanes that hold the row maximum (a second, integer butterfly)
-                    int m0i = o0 == m0 ? rix[ARGS ? rt : 0][0] * 16 + ccol : 0x7fff, m1i = o1 == m1 ? rix[ARGS ? rt : 0][1] * 16 + ccol : 0x7fff;
-                    int m2i = o2 == m2 ? rix[ARGS ? rt : 0][2] * 16 + ccol : 0x7fff, m3i = o3 == m3 ? rix[ARGS ? rt : 0][3] * 16 + ccol : 0x7fff;
-                    {
-                        int &m0 = m0i, &m1 = m1i, &m2 = m2i, &m3 = m3i;   // the macro names its operands m0..m3
-                        VLG_AM_DPP4("v_min_i32_dpp", "quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf");
-                        VLG_AM_DPP4("v_min_i32_dpp", "quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf");
-                        VLG_AM_DPP4("v_min_i32_dpp", "row_half_mirror row_mask:0xf bank_mask:0xf");
-                        VLG_AM_DPP4("v_min_i32_dpp", "row_mirror row_mask:0xf bank_mask:0xf");
-                    }
-                    int ri = m3i;
-                    ri = is2 ? m2i : ri;
-                    ri = is1 ? m1i : ri;
-                    ri = is0 ? m0i : ri;
-                    if (ccol < 4 && rt * 16 < qlim) xa.argV[at0 + rt * 16] = (uint16_t)ri;
-                }
                 if (ccol < 4 && rt * 16 < qlim) out_maxV[at0 + rt * 16] = res;
             }
         };
@@ -626,17 +604,13 @@ __global__ __launch_bounds__(kAMThreads, 2) void align_max_kernel(
             // tiles (-> row maxima) is kept per row tile, the one over the row tiles (-> column maxima) per column tile
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) rmx[rt] = f32x4{ninf, ninf, ninf, ninf};
-            const bool prior_on = ARGS && xa.pen != nullptr && a == b;   // wave-uniform: the diagonal pair of this caption
 #pragma unroll 1
             for (int ct = 0; ct < 3; ++ct) {
                 bf16x8 bfr[KCH];
 #pragma unroll
                 for (int kc = 0; kc < KCH; ++kc) bfr[kc] = *reinterpret_cast<const bf16x8*>(tb + ct * 256 + foff[kc]);
                 f32x4 cmx = f32x4{ninf, ninf, ninf, ninf};
-                int cix[4] = {0, 0, 0, 0};   // ARGS: row tile that holds the running column maximum (first one: rt ascends)
                 const unsigned ckc = (ckl >> ct) & 1u;
-                const float* prow = nullptr;   // prior row of this lane's column segment
-                if (prior_on) prow = xa.pen + (size_t)bc * Q * xa.n_seg + xa.seg_of_v[min(ct * 16 + ccol, V - 1)];
 #pragma unroll
                 for (int rt = 0; rt < RT; ++rt) {
                     f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -646,26 +620,13 @@ __global__ __launch_bounds__(kAMThreads, 2) void align_max_kernel(
 #pragma unroll
                         for (int n = 0; n < 4; ++n) acc[n] = ((tkeep >> (rt * 4 + n)) & ckc) ? acc[n] : neg_inf;
                     }
-                    if (prior_on) {   // joint.py:466-469
-#pragma unroll
-                        for (int n = 0; n < 4; ++n) acc[n] -= prow[(size_t)min(q0 + rt * 16 + crow + n, Q - 1) * xa.n_seg];
-                    }
 #pragma unroll
                     for (int n = 0; n < 4; ++n) {
-                        if (ARGS) {   // strict >: the earlier column tile / row tile keeps a tie
-                            const bool up = acc[n] > rmx[rt][n];
-                            rmx[rt][n] = up ? acc[n] : rmx[rt][n];
-                            rix[ARGS ? rt : 0][n] = up ? ct : rix[ARGS ? rt : 0][n];
-                            const bool upc = acc[n] > cmx[n];
-                            cmx[n] = upc ? acc[n] : cmx[n];
-                            cix[n] = upc ? rt : cix[n];
-                        } else {
-                            rmx[rt][n] = fmaxf(rmx[rt][n], acc[n]);
-                            cmx[n] = fmaxf(cmx[n], acc[n]);
-                        }
+                        rmx[rt][n] = fmaxf(rmx[rt][n], acc[n]);
+                        cmx[n] = fmaxf(cmx[n], acc[n]);
                     }
                 }
-                if (out_maxQ && !ARGS) {   // column maxima of this column tile: within-lane over the four rows, then across the row groups
+                if (out_maxQ) {   // column maxima of this column tile: within-lane over the four rows, then across the row groups
                     float m = fmaxf(fmaxf(cmx[0], cmx[1]), fmaxf(cmx[2], cmx[3]));
                     // lanes l, l^16, l^32, l^48 hold the same column: v_permlane16/32_swap with both operands = m return
                     // (own, partner) in some order on every lane -- no LDS round trip (ds_bpermute costs one per step)
@@ -683,54 +644,17 @@ __global__ __launch_bounds__(kAMThreads, 2) void align_max_kernel(
                         *dst = q0 == 0 ? m : fmaxf(*dst, m);   // the same wave handles every row group of (b, a)
                     }
                 }
-                if (out_maxQ && ARGS) {
-                    // (value, query) pairs: the larger value wins, equal values keep the smaller query.  Within the lane the four
-                    // rows 16 cix + 4 g + n; then the other row groups g (same column) by v_permlane16/32_swap of both halves.
-                    float m = cmx[0];
-                    int qi = cix[0] * 16 + crow;
-#pragma unroll
-                    for (int n = 1; n < 4; ++n) {
-                        const int qn = cix[n] * 16 + crow + n;
-                        const bool take = cmx[n] > m || (cmx[n] == m && qn < qi);
-                        m = take ? cmx[n] : m;
-                        qi = take ? qn : qi;
-                    }
-                    qi += q0;
-#pragma unroll
-                    for (int step = 0; step < 2; ++step) {
-                        const auto rv = step == 0 ? __builtin_amdgcn_permlane16_swap(__float_as_uint(m), __float_as_uint(m), false, false)
-                                                  : __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
-                        const auto ri = step == 0 ? __builtin_amdgcn_permlane16_swap((unsigned)qi, (unsigned)qi, false, false)
-                                                  : __builtin_amdgcn_permlane32_swap((unsigned)qi, (unsigned)qi, false, false);
-                        // (r[0], r[1]) = (own, partner) in some order, the same order for both swaps: fold both halves
-                        const float va = __uint_as_float(rv[0]), vb = __uint_as_float(rv[1]);
-                        const int ia = (int)ri[0], ib = (int)ri[1];
-                        const bool tb_ = vb > va || (vb == va && ib < ia);
-                        m = tb_ ? vb : va;
-                        qi = tb_ ? ib : ia;
-                    }
-                    const int v = ct * 16 + ccol;
-                    if (b < B && lane < 16 && v < V) {
-                        const size_t at = ((size_t)bc * A + a) * V + v;
-                        if (q0 == 0 || m > out_maxQ[at]) {   // later row groups only win with a strictly larger value
-                            out_maxQ[at] = m;
-                            xa.argQ[at] = (uint16_t)qi;
-                        }
-                    }
-                }
             }
             row_epilogue(a);
-#ifndef VLG_ABL_AM_NOBARRIER   // tools/ ablation: what the per-image barrier costs (results are wrong without it)
             __syncthreads();
-#endif
         }
     }
 }
 #undef VLG_AM_DPP4
 
 // =====================================================================================================
-// The grounding loss's maxima WITH their positions (joint.py:446-483), round 3.  align_max_kernel<true, 3> above spends its
-// time on the vector ALU, not on the matrix cores: per image and 48-row pass 36 MFMAs (576 cycles) against ~520 vector
+// The grounding loss's maxima WITH their positions (joint.py:446-483), round 3.  The round-2 kernel (align_max_kernel carrying a
+// position next to each running maximum in 48-row passes; since removed) spent its time on the vector ALU, not on the matrix cores: per image and 48-row pass 36 MFMAs (576 cycles) against ~520 vector
 // instructions (2100 cycles) -- (compare, select, select) per element and direction to carry a position next to each running
 // maximum, and for the maxima over regions a 16-lane DPP butterfly per accumulator register, once for the value and once for
 // the position -- with two wavefronts per SIMD to hide the dependent DPP chains behind (217 registers): 267 us at config-2.
@@ -974,13 +898,7 @@ __global__ __launch_bounds__(kAMThreads) void align_argmax_kernel(
                 }
             }
             // ---- maxima over the regions: S^T, one query tile at a time ----
-            // (tools/time_argmax_ablation.sh: -DVLG_ABL_AM_NOST / _NOS drop one of the two products, _NOSEARCH the first-equal searches -- wrong
-            //  results, measured ceilings: HISTORY.md section 3.1a)
-#ifdef VLG_ABL_AM_NOST
-            if (false) {
-#else
             if (out_maxV) {   // (kernel-uniform)
-#endif
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) {
                 f32x4 st[3];   // rows = regions 16 ct + 4 g + n, column = query 16 rt + ccol
@@ -1010,11 +928,7 @@ __global__ __launch_bounds__(kAMThreads) void align_argmax_kernel(
                                   am_max3(am_max3(st[1][2], st[1][3], st[2][0]), t3, t3));
                 m = am_xg_max(m);
                 unsigned vi = 0;
-#ifdef VLG_ABL_AM_NOSEARCH
-                if (false) {
-#else
                 if (ARGS) {
-#endif
                     vi = am_first_eq12<0, 1, 2, 3, 16, 17, 18, 19, 32, 33, 34, 35>(BIG, m, st[0][0], st[0][1], st[0][2], st[0][3], st[1][0], st[1][1],
                                                                                     st[1][2], st[1][3], st[2][0], st[2][1], st[2][2], st[2][3]);
                     vi = am_xg_min(vi + (unsigned)crow);
@@ -1063,11 +977,7 @@ __global__ __launch_bounds__(kAMThreads) void align_argmax_kernel(
             }
             }   // out_maxV
             // ---- maxima over the queries: S, one region tile at a time ----
-#ifdef VLG_ABL_AM_NOS
-            if (false) {
-#else
             if (HASQ) {
-#endif
 #pragma unroll
                 for (int ct = 0; ct < 3; ++ct) {
                     f32x4 sq[RT];   // rows = queries 16 rt + 4 g + n, column = region 16 ct + ccol
@@ -1116,11 +1026,7 @@ __global__ __launch_bounds__(kAMThreads) void align_argmax_kernel(
                     m = am_xg_max(m);
                     // position code 4 rt + n (query 16 rt + 4 g + n; 80.. is no inline constant), later row tiles first
                     unsigned qi = 0;
-#ifdef VLG_ABL_AM_NOSEARCH
-                    if (false) {
-#else
                     if (ARGS) {
-#endif
                         unsigned qc = BIG;
                         if constexpr (RT == 6)
                             qc = am_first_eq12<12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23>(BIG, m, sq[RT - 3][0], sq[RT - 3][1], sq[RT - 3][2], sq[RT - 3][3], sq[RT - 2][0],
@@ -1384,11 +1290,6 @@ __global__ __launch_bounds__(kAMThreads, VLG_AF_WPE) void align_full_kernel(
                     for (int n = 0; n < 4; ++n) vkeep |= (unsigned)ckeep_s[buf][ct * 16 + 4 * g + n] << (4 * ct + n);
                 v_masked = __builtin_amdgcn_ballot_w64(vkeep != 0xfffu) != 0;
             }
-            // (tools/time_align_full_ablation.sh: -DVLG_ABL_AF_NOMFMA drops the products and the LDS writes, -DVLG_ABL_AF_NOSTORE the global stores --
-            //  wrong results, measured ceilings: HISTORY.md section 3)
-#ifdef VLG_ABL_AF_NOMFMA
-            if (false)
-#endif
 #pragma unroll 1
             for (int ct = 0; ct < 3; ++ct) {
                 bf16x8 vf[KCH];   // A operand: regions 16 ct + (lane & 15) of the image tile
@@ -1411,19 +1312,12 @@ __global__ __launch_bounds__(kAMThreads, VLG_AF_WPE) void align_full_kernel(
             // linear copy-out of the wave's block (same layout as the output): all reads first, then contiguous 1 KB stores
             __builtin_amdgcn_wave_barrier();
             if (b < B) {
-#ifdef VLG_ABL_AF_SEQ   // (ablation: the same bytes, but the eight waves of a workgroup write NEIGHBOURING chunks instead of chunks 3 MB apart)
-#ifndef VLG_ABL_AF_SEQ_STRIDE
-#define VLG_ABL_AF_SEQ_STRIDE ((size_t)Q * V)
-#endif
-                f32x4* dst4 = reinterpret_cast<f32x4*>(out_full + ((((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kAMWaves + wave) * a_per_block + i) * VLG_ABL_AF_SEQ_STRIDE);
-#else
                 f32x4* dst4 = reinterpret_cast<f32x4*>(out_full + (((size_t)bc * A + a) * Q + q0) * V);
-#endif
                 const f32x4* src4 = reinterpret_cast<const f32x4*>(otile);
                 // (round 5) store instruction k covers the 16-byte pieces 64 k - sh + lane, sh = the chunk's first piece within its 128-byte line:
                 // every instruction then writes eight WHOLE lines -- a chunk is Q V floats = 11 808 bytes at config-2, 32 bytes past a line
                 // boundary, and with pieces 64 k + lane every one of the twelve instructions split two lines with its neighbour (measured on the
-                // store stream alone: 181 -> 161 us with line-aligned chunks; tools/time_align_full_ablation.sh)
+                // store stream alone: 181 -> 161 us with line-aligned chunks)
                 const int sh = (int)((reinterpret_cast<uintptr_t>(dst4) >> 4) & 7);
                 constexpr int NC = (RT * 16 * 48 / 4 + 63) / 64 + 1;   // V <= 48; + 1: the shifted last pieces
                 // non-temporal: the 774 MB tensor is written once and read by a later kernel, never by this one (round 4:
@@ -1438,21 +1332,11 @@ __global__ __launch_bounds__(kAMThreads, VLG_AF_WPE) void align_full_kernel(
 #pragma unroll
                     for (int k = 0; k < NH; ++k) {
                         const int j = lane + 64 * (half * NH + k) - sh;
-#ifdef VLG_ABL_AF_NOSTORE
-                        if (half * NH + k < NC && j >= 0 && j < n4 && tv[k][0] == 1.2345e-33f) __builtin_nontemporal_store(tv[k], dst4 + j);
-#elif defined(VLG_ABL_AF_PLAINST)
-                        if (half * NH + k < NC && j >= 0 && j < n4) dst4[j] = tv[k];
-#else
                         if (half * NH + k < NC && j >= 0 && j < n4) __builtin_nontemporal_store(tv[k], dst4 + j);
-#endif
                     }
                 }
             }
-#ifdef VLG_ABL_AF_LDSBAR
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#else
             __syncthreads();   // (an LDS-only barrier -- s_waitcnt lgkmcnt(0) + s_barrier, leaving the stores in flight -- measured the same: 0.197 ms)
-#endif
         }
     }
 }
@@ -1463,9 +1347,6 @@ static int launch_align_full(const void* txt, const void* vis, const uint8_t* tm
     int a_per_block = (int)(((long)A * by + 255) / 256);
     if (a_per_block < 8) a_per_block = 8;
     if (a_per_block > A) a_per_block = A;
-#ifdef VLG_AF_APB   // (tools/ A/B builds)
-    a_per_block = VLG_AF_APB;
-#endif
     dim3 grid((A + a_per_block - 1) / a_per_block, by);
     const size_t lds = sizeof(float) * (size_t)kAMWaves * (VLG_AF_RT * 16) * V;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(align_full_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1574,34 +1455,33 @@ static int launch_align_max(const void* txt, const void* vis, const uint8_t* tma
     // positions wanted: both products on the matrix cores (172 vs 267 us at config-2).  The maxima alone stay with align_max_kernel:
     // without the searches that one is not vector-ALU bound, and the second product only costs (ARGS = false measured: 149 vs 130 us)
     if constexpr (ARGS) {
-        if (!VLG_ENV("VLG_ALIGN_ARGMAX_OLD")) {   // (the env switch: tools/ A-B timing only)
-            if (out_maxQ)
+        if (out_maxQ)
 #define VLG_AAM(HQ, MU)                                                                                                       \
     hipLaunchKernelGGL((align_argmax_kernel<HQ, true, MU>), grid, dim3(kAMThreads), 0, s, (const uint16_t*)txt, (const uint16_t*)vis, tmask, \
                        vmask, B, A, Q, V, neg_inf, out_maxV, out_maxQ, a_per_block, xa, AlignParts{nullptr, nullptr, nullptr})
-                { if (ng > 1) VLG_AAM(true, true); else VLG_AAM(true, false); }
-            else
-                { if (ng > 1) VLG_AAM(false, true); else VLG_AAM(false, false); }
+            { if (ng > 1) VLG_AAM(true, true); else VLG_AAM(true, false); }
+        else
+            { if (ng > 1) VLG_AAM(false, true); else VLG_AAM(false, false); }
 #undef VLG_AAM
-            if (xa.pen) {
-                if (int rc = check_launch("align_argmax_kernel")) return rc;
-                // wavefronts per diagonal pair: the region groups of a many-column image are dealt round.  Eight (round 6: 157 KB of score
-                // tiles, the whole LDS of a CU) for the shipped layout's 29 groups: there are only B workgroups, the kernel is a chain of
-                // dependent rounds, and 4 rounds instead of 8 took it from 162 to ~90 us at B = 64
-                const int pd_nw = ng >= 8 ? 8 : ng >= 4 ? 4 : 1;
-                const size_t pd_lds = sizeof(float) * ((size_t)pd_nw * kPdRT * 16 * kPdP + (size_t)pd_nw * 256);
-                hipError_t pe = hipFuncSetAttribute(reinterpret_cast<const void*>(align_prior_diag_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pd_lds);
-                if (pe != hipSuccess) return set_error((int)pe, "hipFuncSetAttribute: %s", hipGetErrorString(pe));
-                hipLaunchKernelGGL(align_prior_diag_kernel<1>, dim3(std::min(A, B)), dim3(64 * pd_nw), pd_lds, s, (const uint16_t*)txt, (const uint16_t*)vis,
-                                   tmask, vmask, B, A, Q, V, neg_inf, out_maxV, out_maxQ, xa, AlignParts{nullptr, nullptr, nullptr});
-                return check_launch("align_prior_diag_kernel");
-            }
-            return check_launch("align_argmax_kernel");
+        if (xa.pen) {
+            if (int rc = check_launch("align_argmax_kernel")) return rc;
+            // wavefronts per diagonal pair: the region groups of a many-column image are dealt round.  Eight (round 6: 157 KB of score
+            // tiles, the whole LDS of a CU) for the shipped layout's 29 groups: there are only B workgroups, the kernel is a chain of
+            // dependent rounds, and 4 rounds instead of 8 took it from 162 to ~90 us at B = 64
+            const int pd_nw = ng >= 8 ? 8 : ng >= 4 ? 4 : 1;
+            const size_t pd_lds = sizeof(float) * ((size_t)pd_nw * kPdRT * 16 * kPdP + (size_t)pd_nw * 256);
+            hipError_t pe = hipFuncSetAttribute(reinterpret_cast<const void*>(align_prior_diag_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pd_lds);
+            if (pe != hipSuccess) return set_error((int)pe, "hipFuncSetAttribute: %s", hipGetErrorString(pe));
+            hipLaunchKernelGGL(align_prior_diag_kernel<1>, dim3(std::min(A, B)), dim3(64 * pd_nw), pd_lds, s, (const uint16_t*)txt, (const uint16_t*)vis,
+                               tmask, vmask, B, A, Q, V, neg_inf, out_maxV, out_maxQ, xa, AlignParts{nullptr, nullptr, nullptr});
+            return check_launch("align_prior_diag_kernel");
         }
+        return check_launch("align_argmax_kernel");
+    } else {
+        hipLaunchKernelGGL((align_max_kernel<6>), grid, dim3(kAMThreads), 0, s, (const uint16_t*)txt, (const uint16_t*)vis, tmask, vmask, B, A, Q, V,
+                           neg_inf, out_maxV, out_maxQ, a_per_block);
+        return check_launch("align_max_kernel");
     }
-    hipLaunchKernelGGL((align_max_kernel<ARGS, ARGS ? 3 : 6>), grid, dim3(kAMThreads), 0, s, (const uint16_t*)txt, (const uint16_t*)vis,
-                       tmask, vmask, B, A, Q, V, neg_inf, out_maxV, out_maxQ, a_per_block, xa);
-    return check_launch("align_max_kernel");
 }
 
 // =====================================================================================================
@@ -1814,15 +1694,9 @@ __global__ __launch_bounds__(256) void align_bwd_transpose_kernel(const T* __res
 // together in every kernel of this shape, the RE-STREAMED features were more than half of what bounds it.  NF = 2 halves them.
 // four consecutive cotangent words (4-byte aligned).  (Round 4: a NON-TEMPORAL load here -- the cotangent is read once per side --
 // measured 0.53 -> 0.59 ms for the call: the second side's pass finds part of the 774 MB in the Infinity Cache only if the first
-// side's loads were allowed to stay there.  -DVLG_BWD_NT selects it.)
-typedef float ab_g4_t __attribute__((ext_vector_type(4), aligned(4)));
+// side's loads were allowed to stay there.)
 __device__ __forceinline__ float4 ld_g4(const char* p) {
-#ifdef VLG_BWD_NT
-    const ab_g4_t v = __builtin_nontemporal_load(reinterpret_cast<const ab_g4_t*>(p));
-    return make_float4(v[0], v[1], v[2], v[3]);
-#else
     return *reinterpret_cast<const float4*>(p);
-#endif
 }
 
 template <bool KCONTIG, int NKC, int MT, int CW, int NT, int FS, int NF = 1>
@@ -2220,7 +2094,7 @@ int vlg_bilinear_align(const void* txt, const void* vis, const uint8_t* tmask, c
                                                           out_diag, s, AlignArgs{nullptr, nullptr, 0, nullptr, nullptr}, true);
     }
     // (eight waves' output blocks of 96 x V floats next to the 24 KB image tiles: V <= 44 fits the 160 KB LDS)
-    if (!f32in && d == 128 && out_full && !out_maxV && !out_maxQ && !out_diag && V <= 44 && V % 4 == 0 && !VLG_ENV("VLG_ALIGN_FULL_OLD"))
+    if (!f32in && d == 128 && out_full && !out_maxV && !out_maxQ && !out_diag && V <= 44 && V % 4 == 0)
         return launch_align_full(txt, vis, tmask, vmask, B, A, Q, V, neg_inf, out_full, s);   // stores straight from the accumulators
     if (!f32in && d == 128) { VLG_MFMA(false, 4); }
     if (!f32in && d == 64) { VLG_MFMA(false, 2); }
@@ -2250,13 +2124,14 @@ int vlg_bilinear_align(const void* txt, const void* vis, const uint8_t* tmask, c
     return check_launch("align_kernel");
 }
 
-// bf16 features, d = 128, at most 96 rows and 96 contraction positions per pair: the split-term path on the bf16 matrix cores
+// d = 128, at most 96 rows and 96 contraction positions per pair: the split-term path on the bf16 matrix cores (fp32 features as hi + lo parts).
+// The dtype test is the accepted set: the workspace query passes in_dtype on unchecked, and an unknown one must size nothing.
 static bool bwd_split_ok(int in_dtype, int d, int M, int K) {
-    return (in_dtype == VLG_BF16 || (in_dtype == VLG_F32 && !VLG_ENV("VLG_BWD_F32_EXACT"))) && d == 128 && M <= 96 && K <= 96;
+    return (in_dtype == VLG_BF16 || in_dtype == VLG_F32) && d == 128 && M <= 96 && K <= 96;
 }
 
 // caption side, two pairs per step on one concatenated scratch: short quad-aligned contraction
-static bool bwd_concat_ok(int K) { return (K & 3) == 0 && K >= 4 && 2 * K <= 96 && !VLG_ENV("VLG_BWD_NOCONCAT"); }
+static bool bwd_concat_ok(int K) { return (K & 3) == 0 && K >= 4 && 2 * K <= 96; }
 static size_t bwd_concat_pitch(int O, int K) { return ((size_t)O * K + 96 + 7) / 8 * 8; }
 
 size_t vlg_bilinear_align_backward_workspace(int B, int A, int Q, int V, int d, int in_dtype) {
@@ -2301,10 +2176,9 @@ int vlg_bilinear_align_backward(const float* grad_out, const void* txt, const vo
             hipLaunchKernelGGL(align_bwd_transpose_kernel<uint16_t>, dim3(O, Kp / 32), dim3(256), 0, s, (const uint16_t*)feat, km, K, Kp,
                                featT, (uint16_t*)nullptr);
         // bf16 features: two fixed indices per workgroup share each staged feature tile (12 waves, one block per CU)
-        const int nf = (!f32feat && fixn >= 64 && !VLG_ENV("VLG_BWD_NF1")) ? 2 : 1;
+        const int nf = (!f32feat && fixn >= 64) ? 2 : 1;
         int split = 1;   // the chip covered at least once; two-addend atomics are order-free
         if ((long)fixn * 2 <= 1024 * nf && O >= 16) split = 2;
-        if (const char* e = VLG_ENV("VLG_BWD_SPLIT")) split = atoi(e) >= 2 ? 2 : 1;
         const int opb = (O + split - 1) / split;
         if (split > 1) {
             hipError_t e = hipMemsetAsync(out, 0, sizeof(float) * (size_t)fixn * M * 128, s);
@@ -2347,7 +2221,6 @@ int vlg_bilinear_align_backward(const float* grad_out, const void* txt, const vo
         // order-free (a + b == b + a; three or more are not associative in fp32): the split stops at 2 -- bit-reproducible
         int split = 1;
         if ((long)gx * fixn < 768 && O / 2 >= 16) split = 2;
-        if (const char* e = VLG_ENV("VLG_BWD_SPLIT")) split = atoi(e) >= 2 ? 2 : 1;   // tools/ experiments only
         const int opb = (O + split - 1) / split;
         if (split > 1) {
             hipError_t e = hipMemsetAsync(out, 0, sizeof(float) * (size_t)fixn * M * d, s);
@@ -2384,9 +2257,8 @@ int vlg_bilinear_align_backward(const float* grad_out, const void* txt, const vo
         const long pitch = (long)bwd_concat_pitch(A, V);
         hipLaunchKernelGGL(align_bwd_concat_transpose_kernel, dim3((unsigned)((pitch + 31) / 32)), dim3(256), 0, s, (const uint16_t*)vis,
                            vmask, A * V, pitch, visT);
-        const int nf = (B >= 64 && !VLG_ENV("VLG_BWD_NF1")) ? 2 : 1;
+        const int nf = B >= 64 ? 2 : 1;
         int split = ((long)B * 2 <= 1024 * nf && A >= 16) ? 2 : 1;
-        if (const char* e = VLG_ENV("VLG_BWD_SPLIT")) split = atoi(e) >= 2 ? 2 : 1;
         const int opb = ((A + split - 1) / split + 1) & ~1;   // even: a step's tile rows start on 16-byte boundaries of featC
         if (split > 1) {
             hipError_t e = hipMemsetAsync(grad_txt, 0, sizeof(float) * (size_t)B * Q * 128, s);
@@ -2452,15 +2324,13 @@ static int grounding_loss_impl(const void* txt, const void* vis, const uint8_t* 
                                                                          wsf + p.off_maxV, wsf + p.off_maxQ, nullptr, s, xa)        \
              : launch_align_mfma<F32, KCHV, true, true, VLG_GA_RTB>(txt, vis, tmask, vmask, B, B, Q, V, neg_inf, nullptr,               \
                                                                     wsf + p.off_maxV, wsf + p.off_maxQ, nullptr, s, xa)
-    // shared image tiles: align_argmax_kernel, any number of region groups (VLG_ALIGN_ARGMAX_OLD: the round-2 kernel for V <= 48)
-    if (!f32in && d == 128 && (V <= kAMRows || !VLG_ENV("VLG_ALIGN_ARGMAX_OLD")) && !VLG_ENV("VLG_GROUND_OLD_ALIGN"))
+    // d = 128: shared image tiles (align_argmax_kernel), any number of region groups; d = 64 / 32: the per-wave MFMA path with positions
+    if (!f32in && d == 128)
         rc = launch_align_max<true>(txt, vis, tmask, vmask, B, B, Q, V, neg_inf, wsf + p.off_maxV, wsf + p.off_maxQ, s, xa);
-    else if (!f32in && d == 128) VLG_GA(false, 4);
     else if (!f32in && d == 64) VLG_GA(false, 2);
     else if (!f32in && d == 32) VLG_GA(false, 1);
-    else if (f32in && d == 128 && Q <= 65535 && !VLG_ENV("VLG_ALIGN_F32_EXACT"))   // two fp16 parts per feature on the shared-image-tile kernel
+    else if (f32in && d == 128)   // two fp16 parts per feature on the shared-image-tile kernel (Q <= 65535: checked above)
         rc = launch_align_argmax_f32(txt, vis, tmask, vmask, B, B, Q, V, neg_inf, wsf + p.off_maxV, wsf + p.off_maxQ, s, xa, wsf + p.off_parts);
-    else if (f32in && d == 128) VLG_GA(true, 8);
     else if (f32in && d == 64) VLG_GA(true, 4);
     else if (f32in && d == 32) VLG_GA(true, 2);
     else return set_error(VLG_ERR_SHAPE, "grounding_loss: d=%d (supported: 32, 64, 128)", d);
@@ -2522,9 +2392,8 @@ int vlg_align_reduced(const void* txt, const void* vis, const uint8_t* tmask, co
                                                                    wsf + p.off_maxV, nullptr, nullptr, s, xa)                      \
              : launch_align_mfma<F32, KCHV, true, true, 3>(txt, vis, tmask, vmask, B, B, Q, V, neg_inf, nullptr, wsf + p.off_maxV, \
                                                            nullptr, nullptr, s, xa)
-    if (!f32in && d == 128 && (V <= kAMRows || !VLG_ENV("VLG_ALIGN_ARGMAX_OLD")) && !VLG_ENV("VLG_GROUND_OLD_ALIGN"))   // row maxima + positions only
+    if (!f32in && d == 128)   // row maxima + positions only
         rc = launch_align_max<true>(txt, vis, tmask, vmask, B, B, Q, V, neg_inf, wsf + p.off_maxV, nullptr, s, xa);
-    else if (!f32in && d == 128) VLG_RA(false, 4);
     else if (!f32in && d == 64) VLG_RA(false, 2);
     else if (!f32in && d == 32) VLG_RA(false, 1);
     else if (f32in && d == 128) VLG_RA(true, 8);

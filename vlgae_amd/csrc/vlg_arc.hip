@@ -589,7 +589,7 @@ static int dispatch_tri(const void* c, const void* w, const void* p, int M, int 
                         hipStream_t s, float* part = nullptr) {
     if (f32in) {
         int rc;
-        if (part && tri3_applies(M, X, H, Y) && !VLG_ENV("VLG_TRI_F32_EXACT")) rc = launch_tri3_forward(c, w, p, M, X, out, reinterpret_cast<char*>(part), s);   // (part: tri3_fwd_bytes)
+        if (part && tri3_applies(M, X, H, Y)) rc = launch_tri3_forward(c, w, p, M, X, out, reinterpret_cast<char*>(part), s);   // (part: tri3_fwd_bytes)
         else if (Y == 128) rc = launch_tri<true, 8>(c, w, p, M, X, H, out, s);
         else if (Y == 64) rc = launch_tri<true, 4>(c, w, p, M, X, H, out, s);
         else if (Y == 32) rc = launch_tri<true, 2>(c, w, p, M, X, H, out, s);
@@ -1147,7 +1147,7 @@ static int run_tri_backward(const void* child, const void* w, const void* parent
                             int Y, char* ws, const TriBwdPlan& p, float* d_child, float* d_w, float* d_parent, hipStream_t s) {
     using T = typename MfmaCfg<F32IN>::T;
     if constexpr (F32IN) {
-        if (tri3_applies(M, X, H, Y) && dw3_applies(M, X, H, Y) && !VLG_ENV("VLG_TRI_F32_EXACT"))
+        if (tri3_applies(M, X, H, Y) && dw3_applies(M, X, H, Y))
             return run_tri_backward_f16x3((const float*)child, (const float*)w, (const float*)parent, (const float*)g, M, X, H, Y, ws, p, d_child, d_w,
                                           d_parent, s);
     }

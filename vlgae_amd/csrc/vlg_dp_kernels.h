@@ -137,7 +137,6 @@ __device__ __forceinline__ void butterfly_dpp_fused(T* v) {
 
 template <int OPK, int n, typename T>
 __device__ __forceinline__ void butterfly(T* v, int G) {   // G is uniform over the workgroup: no divergence
-#ifndef VLG_NO_FUSED_BUTTERFLY
     if constexpr (n == 3 || n == 4 || n == 6) {
         if (G >= 4) {   // (G is a compile-time constant wherever a segment function inlines this)
             if (G == 4) butterfly_dpp_fused<OPK, 2, n>(v);
@@ -148,7 +147,6 @@ __device__ __forceinline__ void butterfly(T* v, int G) {   // G is uniform over 
             return;
         }
     }
-#endif
     if (G > 1) butterfly_step<OPK, 1, n>(v);
     if (G > 2) butterfly_step<OPK, 2, n>(v);
     if (G > 4) butterfly_step<OPK, 4, n>(v);

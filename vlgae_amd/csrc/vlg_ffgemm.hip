@@ -188,9 +188,6 @@ __device__ __forceinline__ void fg_tile(const FgArgs& a, long long t, const char
         for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt) acc[rt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ks][nt], xf[rt], acc[rt][nt], 0, 0, 0);
-#ifdef VLG_FG_ONE_KSTEP   // tools/ ablation (results are wrong): one of the eight contraction steps
-        break;
-#endif
     }
     const long long row0 = t * kFgRows;
     constexpr bool kPlain = KS > 8;     // the K = 512 image: a plain layer's adjoint (no mask, no draw, no group sum: 128 of its 256 registers hold the weights)
@@ -244,12 +241,8 @@ __device__ __forceinline__ void fg_tile(const FgArgs& a, long long t, const char
 #pragma unroll
                         for (int k = 0; k < 4; ++k) val[k] *= km[rt][nt][k];
                     }
-#ifndef VLG_FG_NOSTORE     // tools/ ablation
                     fg_store4(a.out + (size_t)orow * kFgH + c, val);
                     if (ys) fg_store4(reinterpret_cast<uint16_t*>(ys + (rt * 16 + r) * kFgXPitch) + c, val);
-#else
-                    if (val[0] == 123.456f) fg_store4(a.out + (size_t)orow * kFgH + c, val);
-#endif
                 }
             } else {
                 const int J = f_J, j = (int)(row & (J - 1));
@@ -360,11 +353,7 @@ __device__ __forceinline__ void ff_gemm_act_body(const FgArgs& a, const FgArgs& 
         for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt)
-#ifndef VLG_FG_NOW         // tools/ ablation: every fragment from the first 16 rows of the block
                 wf[ks][nt] = *reinterpret_cast<const bf16x8*>(wb + (size_t)(ks >> 3) * kFgH * kFgH + (size_t)(nt * 16 + r) * KP + (ks & 7) * 32 + kg * 8);
-#else
-                wf[ks][nt] = *reinterpret_cast<const bf16x8*>(a.w + (size_t)r * KP + kg * 8);
-#endif
     } else {      // w [K][ldw], w[k][n] (the eight elements of a fragment are eight rows of w apart: 2-byte reads, once per launch)
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
@@ -497,10 +486,10 @@ int fg_launch_km(const FgArgs& a, int nb, hipStream_t s) {
     return check_launch("ff_gemm_act_kernel");
 }
 
-// the images with their options compiled in: the combinations vlgae_amd.parser_ff / align.linear_kn launch in a training step (VLG_FF_GENERIC=1: the
-// generic image everywhere, A/B timing); any other combination of a C-ABI caller takes the generic image
+// the images with their options compiled in: the combinations vlgae_amd.parser_ff / align.linear_kn launch in a training step;
+// any other combination of a C-ABI caller takes the generic image (options read at run time)
 int fg_launch(const FgArgs& a, int k, int nb, hipStream_t s) {
-    const int m = VLG_ENV("VLG_FF_GENERIC") ? -2 : fg_mode(a);
+    const int m = fg_mode(a);
 #define FG_CASE(KS_, M_) if (m == (M_)) return fg_launch_km<KS_, (M_)>(a, nb, s)
     if (k == 32) {
         FG_CASE(1, kMBwd);
@@ -613,7 +602,7 @@ int vlg_ff_linear_act_chain2(const void* x, int ldx, long long rows, int backwar
     static_assert(lds <= 64 * 1024, "dynamic LDS attribute needed");
     const long long tiles = (rows + kFgRows - 1) / kFgRows;
     const dim3 grid((unsigned)std::min<long long>(tiles, 256));
-    const int ma = VLG_ENV("VLG_FF_GENERIC") ? -2 : fg_mode(a), mb = fg_mode(b);
+    const int ma = fg_mode(a), mb = fg_mode(b);
     if (ma == kMRng && mb == 0) hipLaunchKernelGGL((ff_gemm_act2_kernel<kMRng, 0>), grid, dim3(kFgThreads), lds, (hipStream_t)stream, a, b);
     else if (ma == (kMBwd | kMRng) && mb == (kMBwd | kMJ4 | kMSwap | kMSum))
         hipLaunchKernelGGL((ff_gemm_act2_kernel<kMBwd | kMRng, kMBwd | kMJ4 | kMSwap | kMSum>), grid, dim3(kFgThreads), lds, (hipStream_t)stream, a, b);

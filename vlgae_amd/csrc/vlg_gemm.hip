@@ -103,9 +103,6 @@ __device__ __forceinline__ void tn_body(const uint16_t* __restrict__ A, int lda,
     // register sets of one stage each (kP x 16 bytes per operand and thread), loaded SETS stages ahead of their use
     u32x4 ra[SETS][kP], rb[SETS][kP];
     auto fetch = [&](int set, int ks) {   // rows k_begin + ks + r0 + kRP p
-#ifdef VLG_TN_HOT          // tools/ ablation (results are wrong): every stage re-reads the split's first stage (cache-resident operands)
-        ks = 0;
-#endif
 #pragma unroll
         for (int p = 0; p < kP; ++p) {
             ra[set][p] = __builtin_amdgcn_raw_buffer_load_b128(rs_a, vo_a, (ks + kRP * p) * lda * 2, 0);
@@ -229,11 +226,7 @@ __device__ __forceinline__ void tn_body(const uint16_t* __restrict__ A, int lda,
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = m0 + wm * kQ + i * 16 + 4 * g + r, col = n0 + wn * kQ + j * 16 + (lane & 15);
-#ifdef VLG_TN_NOSTORE      // tools/ ablation (results are wrong): no partial tiles
-                if (row < M && col < N && acc[i][j][r] == 123.456f) out[(size_t)row * N + col] = acc[i][j][r];
-#else
                 if (row < M && col < N) out[(size_t)row * N + col] = acc[i][j][r];
-#endif
             }
     if (CS && want_cs && (lane & 15) == 0) {
 #pragma unroll
@@ -757,10 +750,10 @@ struct TnPlan {
     size_t bytes;
 };
 
-// the tile shape of a product: the 128-tile once both output dimensions fill one (VLG_WGRAD_TILE64 forces the round-3 kernel: A/B timing)
+// the tile shape of a product: the 128-tile once both output dimensions fill one
 // (with both column sums wanted: see wgrad_launch).  Below ~8 tiles of 128 the split count that fills the chip makes the partial tiles -- S x M x N
 // floats written and read back -- cost more than the 64-tile's extra operand traffic: [4 B L, 256]^T [4 B L, 256] measured 23.0 vs 21.8 us.
-inline bool tn_big(int M, int N) { return M >= 128 && N >= 128 && ((M + 127) / 128) * ((N + 127) / 128) >= VLG_TN_BIG_MIN && !VLG_ENV("VLG_WGRAD_TILE64"); }
+inline bool tn_big(int M, int N) { return M >= 128 && N >= 128 && ((M + 127) / 128) * ((N + 127) / 128) >= VLG_TN_BIG_MIN; }
 
 TnPlan plan_tn(int K, int M, int N, bool big, bool f32 = false) {   // (float32 operands: half the stage depth -- four LDS images instead of two)
     const int kTile = big ? 128 : 64, kStage = f32 ? (big ? 32 : 64) : (big ? VLG_TN128_STAGE : VLG_TN64_STAGE);

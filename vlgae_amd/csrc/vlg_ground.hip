@@ -182,17 +182,6 @@ __device__ __forceinline__ void ground_ce_tile_body(float* __restrict__ buf, siz
     }
 }
 
-template <typename W>
-__global__ __launch_bounds__(kCeTileThreads) void ground_ce_tile_kernel(float* __restrict__ buf, size_t fixed_stride, size_t row_stride,
-                                                                        int n, int ncols, int cw_max, const W* __restrict__ w,
-                                                                        const uint16_t* __restrict__ arg,
-                                                                        const uint8_t* __restrict__ self_mask,
-                                                                        const uint8_t* __restrict__ other_mask, int n_other,
-                                                                        float* __restrict__ partial) {
-    ground_ce_tile_body<W>(buf, fixed_stride, row_stride, n, ncols, cw_max, w, arg, self_mask, other_mask, n_other, partial, (int)blockIdx.y,
-                           (int)gridDim.y);
-}
-
 // Both cross-entropies of the grounding loss in ONE launch (round 3): they are independent, 26 us each, and their strips co-reside
 // on a CU -- blockIdx.y < y1: the txt2vis strips (float weights = the marginals), else the vis2txt strips (byte weights = vis_mask).
 struct CeSide {
@@ -809,7 +798,6 @@ __global__ __launch_bounds__(256) void ground_bwd_dense_kernel(
         if (cp == 0 && o + CH < O) chunk_load(o + CH, carg, cval, cpar);   // the chunk after this one: in flight during this step
         // ---- W of this step: clear last step's elements, write this step's (same owner thread: program order) ----
         auto welem = [&](int row, int col) { return reinterpret_cast<uint16_t*>(wt + row * PITCH + col * 2); };
-#ifndef VLG_GD_NOW
         {
             // every read of the staged arrays first (for all PP pairs: independent chains), then the clears and writes.  BRANCH-FREE
             // (round 3): unconditional LDS reads at clamped indices, integer flags, writes that go to the row's pitch padding when
@@ -870,12 +858,10 @@ __global__ __launch_bounds__(256) void ground_bwd_dense_kernel(
                 po_old[q] = col_w ? my_o[q] : -1;
             }
         }
-#endif
         __syncthreads();                                          // W and the tile of this step complete
         // Fragment reads are issued in batches ahead of their MFMAs (sched_barrier pins them there): left to itself hipcc
         // reuses ONE register quad for the B fragments -- read, wait lgkmcnt(0), MFMAs, next read -- which exposes a full
         // LDS latency per fragment.
-#ifndef VLG_GD_NOMFMA
         {
             constexpr int NK = PP * NKC;
             gd_bf16x8 af[2][RT], bf[2][CT];   // two fragment sets: chunk kc+1 is read while chunk kc's MFMAs run
@@ -900,13 +886,10 @@ __global__ __launch_bounds__(256) void ground_bwd_dense_kernel(
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-#endif
         __syncthreads();                                          // every wave is done with the tile and W before they change
-#ifndef VLG_GD_NOSTAGE
         stage_tile(xs);                                           // the next step's pairs
         if (cp + PP == CH && o + PP < O) chunk_store(o + PP, carg, cval, cpar);   // this chunk's last W is built: its arrays make way
         stage_load(min(o + 2 * PP, O - 1), xs);
-#endif
     }
     // accumulator tile: lane l, register n <-> row 4 (l >> 4) + n, column l & 15
 #pragma unroll
@@ -940,15 +923,6 @@ __global__ __launch_bounds__(256) void ground_bwd_dense_kernel(
 // otherwise need a barrier of their own between the last read of a chunk and the store of the next one).  No split of the outer
 // range by default: a block sweeps all partners of its caption / image, the result is written once -- no atomics, no zero fill.
 // =====================================================================================================
-#ifdef VLG_GW_STAMP   // tools/ experiment: per-role cycles from a barrier's release to the arrival at the next one (printed for two blocks)
-#define GW_STAMP_DECL unsigned long long st_busy = 0, st_t = __builtin_amdgcn_s_memtime();
-#define GW_SYNC() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); st_busy += __builtin_amdgcn_s_memtime() - st_t; __syncthreads(); st_t = __builtin_amdgcn_s_memtime(); } while (0)
-#define GW_STAMP_OUT(role) do { if (lane == 0 && (blockIdx.x == 0 || blockIdx.x == 100)) printf("block %d wave %d role %s: %llu cycles busy over %d steps = %llu per step\n", (int)blockIdx.x, wave, role, st_busy, T, st_busy / (unsigned long long)T); } while (0)
-#else
-#define GW_STAMP_DECL
-#define GW_SYNC() __syncthreads()
-#define GW_STAMP_OUT(role)
-#endif
 constexpr int kGwThreads = 768;   // twelve waves: 4 consumers, 2 builders, 4 tile stagers, 2 array stagers
 // KS = 2: the consumers split the contraction axis between two wave pairs (each wave twice the column tiles, half the chunks:
 // fewer fragment reads per MFMA -- the image side's 3 x 2 tiles per wave read 5 fragments per 6 MFMAs and the LDS, not the matrix
@@ -1041,21 +1015,17 @@ __global__ __launch_bounds__(kGwThreads) void ground_bwd_ws_kernel(
         if (SPC < T) chunk_load(o_begin + CHP, carg, cval, cpar);
         __syncthreads();                                 // (chunk 0 visible to the builders)
         __syncthreads();
-        GW_STAMP_DECL
         for (int t = 0; t < T; ++t) {
             const int u = t + 1;
             // the chunk that starts with the NEXT step: its half was last read a whole chunk ago (the current chunk sits in the
             // other half), and the barrier below publishes it
-#ifndef VLG_GW_NOARGS   // tools/ ablations (results are wrong with any of these)
             if (u < T && (u + 1) % SPC == 0 && (u + 1) < T) {
                 const int c = (u + 1) / SPC;
                 chunk_store(c & 1, carg, cval, cpar);
                 if ((c + 1) * SPC < T) chunk_load(o_begin + (c + 1) * CHP, carg, cval, cpar);
             }
-#endif
-            GW_SYNC();
+            __syncthreads();
         }
-        GW_STAMP_OUT("arrays");
         return;
     }
 
@@ -1118,18 +1088,14 @@ __global__ __launch_bounds__(kGwThreads) void ground_bwd_ws_kernel(
         stage_tile(tile0, s0);
         stage_load(o_begin + PP, s0);
         __syncthreads();
-        GW_STAMP_DECL
         for (int t = 0; t < T; ++t) {
             const int u = t + 1;
-#ifndef VLG_GW_NOSTAGE
             if (u < T) {
                 stage_tile(tile0 + (u & 1) * TILE_B, s0);
                 stage_load(o_begin + (u + 1) * PP, s0);
             }
-#endif
-            GW_SYNC();
+            __syncthreads();
         }
-        GW_STAMP_OUT("tiles");
         return;
     }
 
@@ -1209,18 +1175,14 @@ __global__ __launch_bounds__(kGwThreads) void ground_bwd_ws_kernel(
         __syncthreads();                                 // (chunk 0 of the small arrays)
         build(0, wt0, ps_old[0], po_old[0]);
         __syncthreads();
-        GW_STAMP_DECL
         for (int t = 0; t < T; ++t) {
             const int u = t + 1;
-#ifndef VLG_GW_NOBUILD
             if (u < T) {
                 if (u & 1) build(u, wt0 + W_B, ps_old[1], po_old[1]);
                 else build(u, wt0, ps_old[0], po_old[0]);
             }
-#endif
-            GW_SYNC();
+            __syncthreads();
         }
-        GW_STAMP_OUT("build");
         return;
     }
 
@@ -1237,7 +1199,6 @@ __global__ __launch_bounds__(kGwThreads) void ground_bwd_ws_kernel(
     __syncthreads();
     __syncthreads();
     __syncthreads();
-    GW_STAMP_DECL
     for (int t = 0; t < T; ++t) {
         const char* wt = wt0 + (t & 1) * W_B;
         const char* tile = tile0 + (t & 1) * TILE_B;
@@ -1250,7 +1211,6 @@ __global__ __launch_bounds__(kGwThreads) void ground_bwd_ws_kernel(
             for (int c = 0; c < CT; ++c)
                 b[c] = *reinterpret_cast<const gd_bf16x8*>(tile + ((ct0 + c) * 16 + ccol) * PITCH + (kc * 4 + kg) * 16);
         };
-#ifndef VLG_GW_NOMFMA
         frags(ks * NKs, af[0], bf[0]);
 #pragma unroll
         for (int kc = 0; kc < NKs; ++kc) {
@@ -1263,10 +1223,8 @@ __global__ __launch_bounds__(kGwThreads) void ground_bwd_ws_kernel(
                     acc[r][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[kc & 1][r], bf[kc & 1][c], acc[r][c], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
         }
-#endif
-        GW_SYNC();
+        __syncthreads();
     }
-    GW_STAMP_OUT("mfma");
     if (KS == 2) {   // (the producers have left: a barrier counts the waves that are still running)
         float* xch = reinterpret_cast<float*>(smem_raw) + (size_t)w2 * (RT * CT * 4 * 64);
         if (ks == 1) {
@@ -1338,8 +1296,8 @@ static int launch_bwd_dense(const void* txt, const void* vis, const float* gV, c
     auto lds = [](int Kp, int mt, int pp) {
         return (size_t)(kGdD + mt * 16) * (pp * Kp * 2 + 32) + (size_t)kGdChunk * (mt * 16 + Kp) * (2 + 4);
     };
-    // config-2's widths: producer / consumer wavefronts, one block per caption / image, written once (ground_bwd_ws_kernel)
-    const bool ws_ok = !wide && !VLG_ENV("VLG_GD_OLD") && (size_t)B * kGdD * 128 * 2 < ((size_t)1 << 31);   // (32-bit buffer offsets of the tile reads)
+    // config-2's widths: producer / consumer wavefronts, one block per caption / image, written once (ground_bwd_ws_kernel: the caption side
+    // at V <= 64, the image side at V <= 48).  Its tile reads use 32-bit buffer offsets: B * 32 KB < 2^31 for every B <= 65535 the entry point accepts.
     auto lds_ws = [](int Kp, int mt, int pp, int uw) {
         const int kt = (pp * uw + 31) / 32 * 32, chp = pp == 3 ? 6 : kGdChunk;
         return 2 * (size_t)(kGdD + mt * 16) * (kt * 2 + 32) + 2 * (size_t)chp * (mt * 16 + Kp) * (2 + 4);
@@ -1354,13 +1312,13 @@ static int launch_bwd_dense(const void* txt, const void* vis, const float* gV, c
     } while (0)
 #define VLG_WS0(MTV, RWV)                                                                                              \
     do { if (V <= 40) VLG_WS(0, 2, MTV, RWV, 5, 3, 40, visT, g_txt); else VLG_WS(0, 2, MTV, RWV, 8, 2, 64, visT, g_txt); } while (0)
-    const bool both_ws = g_txt && g_vis && ws_ok && V <= 48;
+    const bool both_ws = g_txt && g_vis && V <= 48;
     if (both_ws) {
         hipLaunchKernelGGL(ground_transpose2_kernel, dim3(B, KtV / 32 + KpQ / 32), dim3(256), 0, s, (const uint16_t*)vis, V, KtV, visT, KtV / 32,
                            (const uint16_t*)txt, Q, KpQ, txtT);
         if (int rc = check_launch("ground_transpose2_kernel")) return rc;
     }
-    if (g_txt && ws_ok) {
+    if (g_txt && !wide) {
         if (!both_ws) hipLaunchKernelGGL(ground_transpose_kernel, dim3(B, KtV / 32), dim3(256), 0, s, (const uint16_t*)vis, V, KtV, visT);
         switch ((Q + 15) / 16) {
             case 1: VLG_WS0(1, 1); break;
@@ -1373,7 +1331,7 @@ static int launch_bwd_dense(const void* txt, const void* vis, const float* gV, c
         if (int rc = check_launch("ground_bwd_ws_kernel")) return rc;
         g_txt = nullptr;
     }
-    if (g_vis && ws_ok && V <= 48) {   // (four region tiles: the double buffers do not fit the LDS)
+    if (g_vis && V <= 48) {   // (four region tiles: the double buffers do not fit the LDS)
         if (!both_ws) hipLaunchKernelGGL(ground_transpose_kernel, dim3(B, KpQ / 32), dim3(256), 0, s, (const uint16_t*)txt, Q, KpQ, txtT);
         switch ((V + 15) / 16) {
             case 1: VLG_WS(1, 3, 1, 1, 12, 2, 96, txtT, g_vis); break;
@@ -1386,8 +1344,8 @@ static int launch_bwd_dense(const void* txt, const void* vis, const float* gV, c
 #undef VLG_WS0
 #undef VLG_WS
     if (!g_txt && !g_vis) return 0;
+    // what is left for ground_bwd_dense_kernel: both sides of the wide layouts, and the image side at 48 < V <= 64
     int split = B >= 32 ? 2 : 1;   // two blocks per caption / image (two-addend atomics stay order-free)
-    if (const char* e = VLG_ENV("VLG_GD_SPLIT")) split = atoi(e);
     // wide caption side: B blocks x split must cover the chip, and there are B * n_kc step units to share: deeper splits write
     // partial sums (fixed-order reduce), not atomics
     const int n_kc_v = KtV / 128;
@@ -1410,47 +1368,21 @@ static int launch_bwd_dense(const void* txt, const void* vis, const float* gV, c
         }                                                                                                              \
         hipLaunchKernelGGL(kern, GRID, dim3(256), nb, s, FT, gV, argV, gQ, argQ, coef, B, Q, V, KTOT, NKC_RT, (size_t)(STRIDE), OUT); \
     } while (0)
-    // SEGL: 16-byte segments of a feature row that are staged; config-2's 36 regions need 5 of the 8
-#define VLG_GD(SIDEV, NKCV, MTV, RWV, FT, OUT)                                                                         \
-    do {                                                                                                               \
-        if (SIDEV == 0 && V <= 40) VLG_GD2(SIDEV, NKCV, MTV, RWV, (SIDEV == 0 ? 5 : 12), 2, dim3(B, split), NKCV * 32, 1, 0, FT, OUT); \
-        else VLG_GD2(SIDEV, NKCV, MTV, RWV, (SIDEV == 0 ? 8 : 12), 2, dim3(B, split), NKCV * 32, 1, 0, FT, OUT);        \
-    } while (0)
-    if (g_txt) {   // rows = queries (Q <= 96), contraction over regions
+    if (g_txt) {   // (wide) rows = queries (Q <= 96), contraction over regions
         hipLaunchKernelGGL(ground_transpose_kernel, dim3(B, KtV / 32), dim3(256), 0, s, (const uint16_t*)vis, V, KtV, visT);
-        if (wide) {
-            float* dst = part_txt ? partial : g_txt;
-            VLG_GD2(0, 4, 6, 2, 16, 1, dim3(B, split_txt), KtV, n_kc_v, part_txt ? (size_t)B * Q * kGdD : 0, visT, dst);
-            if (part_txt) {
-                const size_t n4 = (size_t)B * Q * kGdD / 4;
-                hipLaunchKernelGGL(ground_partial_sum_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, partial, split_txt, n4,
-                                   g_txt);
-            }
-        } else {
-            switch ((Q + 15) / 16) {
-                case 1: VLG_GD(0, 2, 1, 1, visT, g_txt); break;
-                case 2: VLG_GD(0, 2, 2, 2, visT, g_txt); break;
-                case 3: VLG_GD(0, 2, 3, 1, visT, g_txt); break;
-                case 4: VLG_GD(0, 2, 4, 2, visT, g_txt); break;
-                case 5: VLG_GD(0, 2, 5, 2, visT, g_txt); break;
-                default: VLG_GD(0, 2, 6, 2, visT, g_txt); break;
-            }
+        float* dst = part_txt ? partial : g_txt;
+        VLG_GD2(0, 4, 6, 2, 16, 1, dim3(B, split_txt), KtV, n_kc_v, part_txt ? (size_t)B * Q * kGdD : 0, visT, dst);
+        if (part_txt) {
+            const size_t n4 = (size_t)B * Q * kGdD / 4;
+            hipLaunchKernelGGL(ground_partial_sum_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, partial, split_txt, n4,
+                               g_txt);
         }
     }
     if (g_vis) {   // rows = regions, contraction over queries (Q <= 96)
         hipLaunchKernelGGL(ground_transpose_kernel, dim3(B, KpQ / 32), dim3(256), 0, s, (const uint16_t*)txt, Q, KpQ, txtT);
-        if (wide) {
-            VLG_GD2(1, 3, 6, 2, 12, 1, dim3(B, 1, (V + 95) / 96), KpQ, 1, 0, txtT, g_vis);   // one pair per step: two blocks fit a CU's LDS
-        } else {
-            switch ((V + 15) / 16) {
-                case 1: VLG_GD(1, 3, 1, 1, txtT, g_vis); break;
-                case 2: VLG_GD(1, 3, 2, 2, txtT, g_vis); break;
-                case 3: VLG_GD(1, 3, 3, 1, txtT, g_vis); break;
-                default: VLG_GD(1, 3, 4, 2, txtT, g_vis); break;
-            }
-        }
+        if (wide) VLG_GD2(1, 3, 6, 2, 12, 1, dim3(B, 1, (V + 95) / 96), KpQ, 1, 0, txtT, g_vis);   // one pair per step: two blocks fit a CU's LDS
+        else VLG_GD2(1, 3, 4, 2, 12, 2, dim3(B, split), KpQ, 1, 0, txtT, g_vis);                 // 48 < V <= 64: four region tiles, two pairs per step
     }
-#undef VLG_GD
 #undef VLG_GD2
     return 0;
 }
@@ -1561,7 +1493,7 @@ int launch_grounding_tail(const void* txt, const void* vis, const uint8_t* tmask
         return Strips{cw, y, sizeof(float) * ((size_t)B * (cw | 1) + kCeTileThreads + 3 * (size_t)cw)};
     };
     const Strips s1 = strips(Q), s2 = strips(V);
-    const bool tiled = s1.lds <= 144 * 1024 && s2.lds <= 144 * 1024 && s1.cw <= kCeTileThreads && s2.cw <= kCeTileThreads && !VLG_ENV("VLG_GROUND_CE_OLD");
+    const bool tiled = s1.lds <= 144 * 1024 && s2.lds <= 144 * 1024 && s1.cw <= kCeTileThreads && s2.cw <= kCeTileThreads;
     // column shares for the streaming kernel: only when B alone leaves CUs idle and there are several 256-column strips
     auto shares = [&](int ncols) {
         const int st = (ncols + kCeThreads - 1) / kCeThreads;
@@ -1573,29 +1505,15 @@ int launch_grounding_tail(const void* txt, const void* vis, const uint8_t* tmask
     // vis2txt: fixed = image a, rows = captions b: x[b][v] = mQ[(b*A + a)*V + v]; weights = vis_mask as 0/1 (joint.py:481,
     // null = all ones); gate: vmask[a][v], tmask[b][argQ]
     if (tiled) {
-        auto k1 = ground_ce_tile_kernel<float>;
-        auto k2 = ground_ce_tile_kernel<uint8_t>;
-        for (auto kp : {std::make_pair((const void*)k1, s1.lds), std::make_pair((const void*)k2, s2.lds)})
-            if (kp.second > 64 * 1024) {
-                hipError_t e = hipFuncSetAttribute(kp.first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kp.second);
-                if (e != hipSuccess) return set_error((int)e, "grounding_loss: hipFuncSetAttribute(%zu): %s", kp.second, hipGetErrorString(e));
-            }
-        if (!VLG_ENV("VLG_GROUND_CE_SPLIT")) {
-            const size_t lds2 = std::max(s1.lds, s2.lds);
-            if (lds2 > 64 * 1024) {
-                hipError_t e = hipFuncSetAttribute((const void*)ground_ce_tile2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-                if (e != hipSuccess) return set_error((int)e, "grounding_loss: hipFuncSetAttribute(%zu): %s", lds2, hipGetErrorString(e));
-            }
-            const CeSide sa{mV, (size_t)B * Q, (size_t)Q, Q, s1.cw, marg, aV, tmask, vmask, V, part, y1};
-            const CeSide sb{mQ, (size_t)V, (size_t)B * V, V, s2.cw, vmask, aQ, vmask, tmask, Q, part2, y2};
-            hipLaunchKernelGGL(ground_ce_tile2_kernel, dim3(B, y1 + y2), dim3(kCeTileThreads), lds2, s, B, sa, sb);
-        } else {
-        hipLaunchKernelGGL(k1, dim3(B, y1), dim3(kCeTileThreads), s1.lds, s, mV, (size_t)B * Q, (size_t)Q, B, Q, s1.cw, marg, aV, tmask, vmask,
-                           V, part);
-        hipLaunchKernelGGL(k2, dim3(B, y2), dim3(kCeTileThreads), s2.lds, s, mQ, (size_t)V, (size_t)B * V, B, V, s2.cw, vmask, aQ, vmask, tmask,
-                           Q, part2);
+        const size_t lds2 = std::max(s1.lds, s2.lds);
+        if (lds2 > 64 * 1024) {
+            hipError_t e = hipFuncSetAttribute((const void*)ground_ce_tile2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+            if (e != hipSuccess) return set_error((int)e, "grounding_loss: hipFuncSetAttribute(%zu): %s", lds2, hipGetErrorString(e));
         }
-    } else {
+        const CeSide sa{mV, (size_t)B * Q, (size_t)Q, Q, s1.cw, marg, aV, tmask, vmask, V, part, y1};
+        const CeSide sb{mQ, (size_t)V, (size_t)B * V, V, s2.cw, vmask, aQ, vmask, tmask, Q, part2, y2};
+        hipLaunchKernelGGL(ground_ce_tile2_kernel, dim3(B, y1 + y2), dim3(kCeTileThreads), lds2, s, B, sa, sb);
+    } else {   // a strip does not fit the LDS tile or the block: the streaming kernel, one launch per direction
         hipLaunchKernelGGL(ground_ce_kernel<float>, dim3(B, y1), dim3(kCeThreads), 0, s, mV, (size_t)B * Q, (size_t)Q, B, Q, marg, aV,
                            tmask, vmask, V, part);
         hipLaunchKernelGGL(ground_ce_kernel<uint8_t>, dim3(B, y2), dim3(kCeThreads), 0, s, mQ, (size_t)V, (size_t)B * V, B, V, vmask, aQ,
@@ -1603,7 +1521,7 @@ int launch_grounding_tail(const void* txt, const void* vis, const uint8_t* tmask
     }
     hipLaunchKernelGGL(ground_sum_kernel, dim3(1), dim3(64), 0, s, part, part2, B * y1, B * y2, num_token, num_token_dev, w_v2t, out_sums,
                        coef);
-    if ((g_txt || g_vis) && in_dtype == VLG_BF16 && d == kGdD && Q <= 96 && V <= 65535 && !VLG_ENV("VLG_GROUND_SPARSE")) {
+    if ((g_txt || g_vis) && in_dtype == VLG_BF16 && d == kGdD && Q <= 96 && V <= 65535) {
         // bf16 features, d = 128, up to 96 queries: the dense route on the matrix cores
         if (int rc = launch_bwd_dense(txt, vis, mV, aV, mQ, aQ, coef, B, Q, V, reinterpret_cast<uint16_t*>(ws + p.off_featT),
                                       ws + p.off_partial, g_txt, g_vis, s))
