@@ -53,14 +53,18 @@ def dmv1o(dec, attach, lengths, semiring=0, grad=True, glogZ=None, nt=16, order=
     return lz, gd, ga
 
 
-def deptree(arc, lengths, semiring=0, grad=True, glogZ=None, nt=16, order=0):
+def deptree(arc, lengths, semiring=0, grad=True, glogZ=None, nt=16, order=0, mode=0):
+    """mode: DepLayout placement mode to emulate (0 = everything in one arena; otherwise the charts that the mode moves to
+    the workspace sit in a second arena: Log inside-outside 1..3, Max walk 1..2, inside only 1)."""
     B, N = arc.shape[:2]
     arc = np.ascontiguousarray(arc, np.float32)
     ln = None if lengths is None else np.ascontiguousarray(lengths, np.int64)
     lz = np.full(B, np.nan, np.float32)
     ga = np.full((B, N, N), np.nan, np.float32) if grad else None
     g = None if glogZ is None else np.ascontiguousarray(glogZ, np.float32)
+    lib().emu_set_dep_mode(int(mode))
     rc = lib().emu_deptree(_p(arc), _p(ln), B, N, 0, semiring, _p(g), _p(lz), _p(ga), nt, order)
+    lib().emu_set_dep_mode(0)
     assert rc == 0
     return lz, ga
 
@@ -79,13 +83,16 @@ def dmv1o_decode(dec, attach, lengths, nt=16, order=0):
     return best, heads
 
 
-def deptree_decode(arc, lengths, nt=16, order=0):
+def deptree_decode(arc, lengths, nt=16, order=0, mode=0):
     B, N = arc.shape[:2]
     arc = np.ascontiguousarray(arc, np.float32)
     ln = np.ascontiguousarray(lengths, np.int64)
     best = np.full(B, np.nan, np.float32)
     heads = np.full((B, N), -1, np.int64)
-    assert lib().emu_deptree_decode(_p(arc), _p(ln), B, N, _p(best), _p(heads), nt, order) == 0
+    lib().emu_set_dep_mode(int(mode))
+    rc = lib().emu_deptree_decode(_p(arc), _p(ln), B, N, _p(best), _p(heads), nt, order)
+    lib().emu_set_dep_mode(0)
+    assert rc == 0
     return best, heads
 
 

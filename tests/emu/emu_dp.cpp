@@ -142,6 +142,7 @@ void run_workgroup(int nt, int order, Body body) {
 constexpr size_t kCanary = 1 << 16;
 static int g_canary_trips = 0;
 static int g_mode = 0;   // DMV placement mode to emulate (0: one carve; 1..3: part of the working set in a second arena = the workspace)
+static int g_dep_mode = 0;   // DepTree placement mode (DepLayout: Log 0..3, Max walk 0..2, inside only 0..1), same two arenas
 
 struct Arena {
     std::vector<unsigned char> buf;
@@ -201,17 +202,19 @@ void emu_rules_one(const vlg::RuleIO<vlg::F32In>& io, int len, float glogZ, floa
 template <int SR, bool BWD, typename In>
 void emu_dep_one(const typename In::T* arc, int len, int N, float glogZ, float* logZ, float* garc, int nt, int order,
                  long long* heads = nullptr) {
-    const vlg::DepLayout L(N, BWD, SR == VLG_SR_MAX, 0);
-    Arena A(L.lds_bytes);
+    const vlg::DepLayout L(N, BWD, SR == VLG_SR_MAX, g_dep_mode);   // the kernel's carve (vlg_dp_kernels.h: carve_dep) over two arenas
+    Arena A(L.lds_bytes), W(L.ws_bytes);
+    auto at = [&](const vlg::Region& r) { return r.lds ? A.at(r.off) : W.at(r.off); };
     vlg::DepCtx c;
     c.Ne = len + 1; c.len = len; c.P = vlg::chart_pitch(N);
-    c.C = (float*)A.at(L.C.off); c.I = (float*)A.at(L.I.off); c.S = (float*)A.at(L.S.off);
-    c.bpS = (unsigned char*)A.at(L.bpS.off); c.bpC = (unsigned char*)A.at(L.bpC.off);
-    c.gCc = (float*)A.at(L.gCc.off); c.gCi = (float*)A.at(L.gCi.off); c.gI = (float*)A.at(L.gI.off);
+    c.C = (float*)at(L.C); c.I = (float*)at(L.I); c.S = (float*)at(L.S);
+    c.bpS = (unsigned char*)at(L.bpS); c.bpC = (unsigned char*)at(L.bpC);
+    c.gCc = (float*)at(L.gCc); c.gCi = (float*)at(L.gCi); c.gI = (float*)at(L.gI);
     run_workgroup(nt, order, [&](int tid, HostX& x) {
         vlg::dep_run<SR, BWD, In>(c, arc, N, glogZ, logZ, garc, heads, tid, nt, x);
     });
     A.check();
+    W.check();
 }
 
 template <typename In>
@@ -260,6 +263,7 @@ int dep_batch(const void* arc_, const int64_t* lengths, int B, int N, int semiri
 extern "C" {
 int emu_canary_trips(void) { return g_canary_trips; }
 void emu_set_dmv_mode(int mode) { g_mode = mode; }
+void emu_set_dep_mode(int mode) { g_dep_mode = mode; }
 // rule-table entry (f32): grads must be zero-filled by the caller; any of them may be null together (inside only)
 int emu_dmv1o_rules(const float* rule, const float* dec, const float* root, int root_per_sentence, const int64_t* token,
                     const unsigned char* head_mask, const int64_t* lengths, int B, int L, int T, int semiring, float fill,

@@ -97,6 +97,33 @@ def test_emu_deptree_golden(path):
     assert emu.canary_trips() == 0
 
 
+@pytest.mark.parametrize("path", [p for p in golden_files("deptree_") if "N81" not in p],
+                         ids=[i for i in golden_ids("deptree_") if "N81" not in i])
+def test_emu_deptree_placement_modes(path):
+    """Every DepLayout placement carved as the kernel carves it -- LDS arena and workspace arena, a canary behind each: the
+    charts a mode moves to the workspace change where the bodies read and write, never what.  Log inside-outside modes 1, 2, 3,
+    Max walk (gradient and decode) modes 1, 2 and inside-only mode 1 are bit-equal to mode 0 and trip no canary."""
+    g = load(path)
+    arc, ln = g["arc"], g["lengths"]
+    want = emu.deptree(arc, ln, 0, glogZ=g["wts"], nt=16, order=0)
+    for mode in (1, 2, 3):
+        got = emu.deptree(arc, ln, 0, glogZ=g["wts"], nt=16, order=mode, mode=mode)
+        assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), mode
+    mwant = emu.deptree(arc, ln, 1, nt=16, order=0)
+    dwant = emu.deptree_decode(arc, ln, nt=16, order=0)
+    assert np.array_equal(mwant[1], g["argmax"])
+    for mode in (1, 2):
+        got = emu.deptree(arc, ln, 1, nt=16, order=mode, mode=mode)
+        assert np.array_equal(got[0], mwant[0]) and np.array_equal(got[1], mwant[1]), mode
+        best, heads = emu.deptree_decode(arc, ln, nt=8, order=mode, mode=mode)
+        assert np.array_equal(best, dwant[0]) and np.array_equal(heads, dwant[1]), mode
+    for sr in (0, 1):
+        lz0, _ = emu.deptree(arc, ln, sr, grad=False, nt=16)
+        lz1, _ = emu.deptree(arc, ln, sr, grad=False, nt=16, order=1, mode=1)
+        assert np.array_equal(lz0, lz1) and np.array_equal(lz0, (want if sr == 0 else mwant)[0])
+    assert emu.canary_trips() == 0
+
+
 def test_emu_ties_take_first_argmax(oracle_mod):
     """All-equal potentials: every tree ties.  torch.max's backward goes to the FIRST maximal index
     (semirings.py:199-200); the kernels' back-pointers must reproduce the same single tree."""

@@ -127,22 +127,48 @@ def test_eval_metrics_kernel_equals_the_restatement_at_config_size(layout):
 
 
 # ------------------------------------------------------------------------------------------------ the MBR decode
-@pytest.mark.parametrize("N", [2, 10, 41, 81])
-def test_mbr_decode_equals_deptree_decode_of_the_valence_sum(N):
-    """vlg_deptree_mbr_decode on [B,N,N,2] float32 marginals = deptree_decode(marginals.sum(-1)) bit for bit (heads and score), ragged lengths."""
-    from vlgae_amd.torch_struct import functional as tsf
+MBR_N = [2, 10, 41, 81, 107, 127, 255]            # the short image, all in LDS, and the Max walk's workspace placements (106/107, 126/127)
+
+
+def mbr_inputs(N):
     B = 9
     g = torch.Generator().manual_seed(N)
     marg = (torch.rand(B, N, N, 2, generator=g) * torch.rand(B, N, N, 1, generator=g)).to(dev())
     lengths = torch.randint(1, N, (B,), generator=g)
     lengths[0] = N - 1
-    lengths = lengths.to(dev())
+    return marg, lengths.to(dev())
+
+
+@pytest.mark.parametrize("N", MBR_N)
+def test_mbr_decode_equals_deptree_decode_of_the_valence_sum(N):
+    """vlg_deptree_mbr_decode on [B,N,N,2] float32 marginals = deptree_decode(marginals.sum(-1)) bit for bit (heads and score), ragged lengths."""
+    from vlgae_amd.torch_struct import functional as tsf
+    marg, lengths = mbr_inputs(N)
     best, heads = tsf.deptree_mbr_decode(marg, lengths)
     want_best, want_heads = tsf.deptree_decode(marg.sum(-1), lengths)
     assert torch.equal(heads, want_heads) and torch.equal(best, want_best)
     assert int((heads[0, 1:] > 0).sum()) >= N - 2          # a tree: one root child, every other word has a head
     with pytest.raises(ValueError, match="float32"):
         tsf.deptree_mbr_decode(marg.bfloat16(), lengths)
+
+
+@pytest.mark.parametrize("N", MBR_N)
+def test_mbr_decode_is_the_best_tree_of_the_fp64_oracle(oracle_mod, N):
+    """The check above compares two launches of one kernel family; this one does not: the heads are a projective single-root tree per
+    sentence, nothing outside it, and the tree's score -- the float32 valence sums added up in float64 -- is within 1e-5 relative of the
+    fp64 oracle's Max-semiring value on those sums, as is the score the launch returns."""
+    from vlgae_amd.torch_struct import functional as tsf
+    marg, lengths = mbr_inputs(N)
+    best, heads = tsf.deptree_mbr_decode(marg, lengths)
+    arc = marg.sum(-1).cpu().numpy()                       # a two-term float32 sum has one order: the values the load stage forms
+    ln, h, got = lengths.cpu().numpy(), heads.cpu().numpy(), best.cpu().numpy()
+    want = oracle_mod.deptree(arc, ln, "max", np.float64, grad=False)[0]
+    for b, n in enumerate(ln):
+        assert oracle_mod.is_projective_tree(h[b], int(n)), b
+        assert h[b, 0] == 0 and not h[b, n + 1:].any(), b
+        score = float(sum(np.float64(arc[b, h[b, c], c]) for c in range(1, n + 1)))
+        assert abs(score - want[b]) <= 1e-5 * max(1.0, abs(want[b])), (b, score, want[b])
+        assert abs(float(got[b]) - want[b]) <= 1e-5 * max(1.0, abs(want[b])), (b, got[b], want[b])
 
 
 # ------------------------------------------------------------------------------------------------ the step on reference-made fixtures
