@@ -87,12 +87,9 @@ def dmv1o(dec, attach, lengths, semiring="log", dtype=np.float32, grad=True, glo
     return logZ.reshape(B, 1), gdec, gatt
 
 
-def dmv1o_rules(attach_rule, dec, root_rule, token, lengths, head_mask=None, semiring="log", dtype=np.float32,
-                grad=True, mask_fill=-1e20):
-    """Scorer -> DP glue of DiscriminativeNDMV._forward restated in numpy (src/model/ldndmv.py:189-209), then the
-    DP oracle, then the adjoint of the glue (scatter-add over repeated tokens).
-      attach_rule [B,L,T,2(dir),2(val)], dec [B,L,2,2,2], root_rule [T] or [1,T] or [B,T], token [B,L] in [0,T)
-    Returns logZ [B,1], grad_rule [B,L,T,2,2], grad_dec [B,L,2,2,2], grad_root [B,T] (per sentence), heads-free."""
+def dmv1o_rules_merged(attach_rule, dec, root_rule, token, head_mask=None, dtype=np.float32, mask_fill=-1e20):
+    """Scorer -> DP glue of DiscriminativeNDMV._forward restated in numpy (src/model/ldndmv.py:189-209): the root-merged
+    potentials (merged_dec [B,N,2,2,2], merged_attach [B,N,N,2]) that the rule tables stand for.  Arguments as dmv1o_rules."""
     dtype = np.dtype(dtype)
     attach_rule = np.asarray(attach_rule, dtype=dtype)
     dec = np.asarray(dec, dtype=dtype)
@@ -116,6 +113,23 @@ def dmv1o_rules(attach_rule, dec, root_rule, token, lengths, head_mask=None, sem
     ma[:, 1:, 1:, :] = attach
     md[:, 0, 1, :, :] = 0
     md[:, 1:] = dec
+    return md, ma
+
+
+def dmv1o_rules(attach_rule, dec, root_rule, token, lengths, head_mask=None, semiring="log", dtype=np.float32,
+                grad=True, mask_fill=-1e20):
+    """The glue of dmv1o_rules_merged, then the DP oracle, then the adjoint of the glue (scatter-add over repeated tokens).
+      attach_rule [B,L,T,2(dir),2(val)], dec [B,L,2,2,2], root_rule [T] or [1,T] or [B,T], token [B,L] in [0,T)
+    Returns logZ [B,1], grad_rule [B,L,T,2,2], grad_dec [B,L,2,2,2], grad_root [B,T] (per sentence), heads-free."""
+    dtype = np.dtype(dtype)
+    attach_rule = np.asarray(attach_rule, dtype=dtype)
+    B, L, T = attach_rule.shape[:3]
+    token = np.asarray(token, dtype=np.int64)
+    bi = np.arange(B)[:, None, None]
+    hi = np.arange(L)[None, :, None]
+    ci = np.arange(L)[None, None, :]
+    tok = token[:, None, :]                                              # child's token id
+    md, ma = dmv1o_rules_merged(attach_rule, dec, root_rule, token, head_mask, dtype, mask_fill)
     logZ, gmd, gma = dmv1o(md, ma, lengths, semiring, dtype, grad=grad)
     if not grad:
         return logZ, None, None, None

@@ -140,9 +140,11 @@ def test_dmv1o_no_grad_and_bf16(ts, oracle_mod):
 
 @pytest.mark.parametrize("B,L,seed", [(64, 40, 11), (16, 63, 12), (8, 80, 13), (4, 120, 14), (33, 5, 15), (2, 254, 16)])
 def test_dmv1o_vs_oracle_random(ts, oracle_mod, B, L, seed):
-    """Fresh seeded inputs at sizes the oracle finishes in seconds; covers the LDS path (N<=66), the
-    workspace paths (N=81: value charts and gI in HBM/L2; N=121: everything but the staging) and the maximum
-    supported size N=255."""
+    """Fresh seeded inputs at sizes the oracle finishes in seconds.  The placement follows the padded width N = L + 1
+    (vlg_dp_core.h: DmvLayout): N = 6 and 41 run the short image with everything in LDS; N = 64 and 81 the Log overlay
+    (mode 1; the Max walk keeps everything in LDS at 64 and moves gI to the workspace at 81); N = 121 and the maximum
+    supported size N = 255 Log mode 3 / walk mode 2, and there the inside-only launch keeps C and I in the workspace.
+    None of these widths is next to a boundary: tests/test_dmv_placements_gpu.py sits on both sides of each."""
     rng = np.random.default_rng(seed)
     dec = rng.standard_normal((B, L, 2, 2, 2)).astype(np.float32)
     dec = dec - np.log(np.exp(dec).sum(-1, keepdims=True))
@@ -310,7 +312,9 @@ def test_dmv1o_long_sentences_full_size(ts, oracle_mod, dt):
     attach = torch.randn(B, L, L, 2, generator=gen)
     root = torch.randn(B, L, generator=gen).log_softmax(-1)
     lengths = torch.randint(1, L + 1, (B,), generator=gen)
-    lengths[0], lengths[1], lengths[2] = L, 61, 62                       # full length; both sides of the all-in-LDS boundary
+    lengths[0], lengths[1], lengths[2] = L, 61, 62                       # full length and two long ones.  The placement follows the padded width
+    # N = 81, not a sentence's length: every sentence of this batch runs in the overlay (mode 1).  The all-in-LDS boundary (N = 62 / 63)
+    # and the others are in tests/test_dmv_placements_gpu.py.
     md, ma = ts.DMV1o.merge(dec.to(dev()), attach.to(dev()), root.to(dev()))
     if dt == "bf16":
         md, ma = md.bfloat16(), ma.bfloat16()
@@ -350,8 +354,9 @@ def test_dmv1o_long_sentences_full_size(ts, oracle_mod, dt):
 @pytest.mark.parametrize("L,scale", [(40, 6.0), (62, 6.0), (63, 6.0), (80, 2.0), (88, 6.0), (89, 6.0), (100, 6.0)],
                          ids=lambda v: str(v))
 def test_dmv1o_long_peaky_sentences(ts, oracle_mod, L, scale):
-    """tools/stress_dp.py's hardest cases in the suite: ragged batches at and beyond the placement-mode
-    boundaries (N = 63 / 64: all-in-LDS -> overlay; 89 / 90: overlay -> workspace) with arc scores of standard deviation up to 6
+    """tools/stress_dp.py's hardest cases in the suite: ragged batches in every Log placement -- N = L + 1 = 41
+    the short image, 63 / 64 and 81 the overlay (mode 1), 89 / 90 and 101 mode 2; these are the first two widths BEYOND the boundaries
+    62 / 63 and 88 / 89, the boundaries themselves are in tests/test_dmv_placements_gpu.py -- with arc scores of standard deviation up to 6
     (|score| up to ~25, logZ ~ 550).  fp32 charts carry values of magnitude ~800 (log2 units) there -- one ulp is 6e-5 and the
     adjoint weights exp(t - out) see it -- so the north-star bound (1e-4 at L = 40) is NOT claimed beyond L = 40:
       L <= 40:  expected counts within 1e-4 of the fp64 oracle even at score scale 6 (the bound of BASELINE.json's north_star)
