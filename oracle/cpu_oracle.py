@@ -20,9 +20,19 @@ _lib = None
 def build(force=False):
     """Compile the oracle with gcc (oracle/Makefile)."""
     srcs = [os.path.join(_HERE, f) for f in ("vlg_oracle.c", "vlg_oracle_impl.h")]
-    stale = (not os.path.exists(_SO)) or any(os.path.getmtime(s) > os.path.getmtime(_SO) for s in srcs)
-    if (force or stale) and not os.environ.get("VLG_ORACLE_SO"):
-        subprocess.run(["make", "-C", _HERE, "-s"], check=True)
+
+    def stale():
+        return (not os.path.exists(_SO)) or any(os.path.getmtime(s) > os.path.getmtime(_SO) for s in srcs)
+
+    if (force or stale()) and not os.environ.get("VLG_ORACLE_SO"):
+        # several processes may get here at once (the ranks of tests/test_dist_gloo.py each import the oracle): one builds, the others
+        # wait for it and find the library fresh.  The Makefile links under a temporary name and renames, so no reader sees half a file.
+        import fcntl
+        os.makedirs(os.path.dirname(_SO), exist_ok=True)
+        with open(os.path.join(os.path.dirname(_SO), ".build.lock"), "w") as lock:
+            fcntl.flock(lock, fcntl.LOCK_EX)
+            if force or stale():
+                subprocess.run(["make", "-C", _HERE, "-s"], check=True)
     return _SO
 
 

@@ -269,3 +269,23 @@ def test_ndmv_potentials_oracle_vs_reference(oracle_mod, path):
     for k in ("x1", "x2", "y1", "y2", "root_rule"):
         ref = g["g_" + k]
         assert np.abs(grads[k] - ref).max() <= 2e-5 * max(1.0, np.abs(ref).max()), k
+
+
+def test_oracle_build_from_several_processes_at_once(tmp_path):
+    """The ranks of tests/test_dist_gloo.py each import the oracle; when its library is missing or stale they all build it.  One must
+    build and the others wait: a rank that loaded the library while another was linking it failed with "file too short".  Run on a copy of
+    the oracle's sources, so the tree's own build is left alone."""
+    import os
+    import shutil
+    import subprocess
+    import sys
+    from conftest import ROOT
+    os.makedirs(tmp_path / "oracle")
+    for f in ("__init__.py", "cpu_oracle.py", "vlg_oracle.c", "vlg_oracle_impl.h", "Makefile"):
+        shutil.copy(os.path.join(ROOT, "oracle", f), tmp_path / "oracle" / f)
+    env = {k: v for k, v in os.environ.items() if k != "VLG_ORACLE_SO"}
+    code = "import oracle; oracle.set_threads(1); assert oracle.max_threads() == 1"
+    procs = [subprocess.Popen([sys.executable, "-c", code], cwd=tmp_path, env=env, stderr=subprocess.PIPE, text=True) for _ in range(4)]
+    errs = [(p.communicate(timeout=300)[1], p.returncode) for p in procs]
+    assert all(rc == 0 for _, rc in errs), [e[-400:] for e, rc in errs if rc]
+    assert [f for f in os.listdir(tmp_path / "oracle" / "_build") if not f.startswith(".")] == ["libvlg_oracle.so"]     # no temporary left behind
