@@ -683,6 +683,41 @@ int vlg_feed_npy_shape(const char* path, int64_t* rows, int64_t* cols);
 int vlg_feed_collate_npy(const char* const* paths, int n, const int32_t* sel, int sel_stride, const int32_t* n_sel, int feat_dim,
                          int box_dim, int max_len, float* feat, float* box, uint8_t* mask, int n_threads);
 
+/* ---- The optimiser step between two training steps (vlgae_amd/optim.py, csrc/vlg_optim.hip) ----
+ *
+ * One call = `clip_grad_norm_(params, max_norm)`, `torch.optim.Adam.step()` (plain Adam: no amsgrad, no maximize) and
+ * `ExponentialLR.step()`, in that order (src/pipeline.py:176-227, config/trainer/train.yaml:14, config/model/optimize/linear.yaml), plus
+ * the refresh of the bf16 tensors the training step reads.  Update k = 1, 2, ...:
+ *   norm = sqrt(sum of g^2 over every tensor), accumulated in float64; coef = min(1, max_norm / (norm + 1e-6)) (max_norm <= 0 or inf: 1;
+ *   a non-finite norm propagates as in torch).  Per element, in float32 on the master value p:
+ *     g = coef g (+ weight_decay p);  m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g^2;
+ *     p -= lr_k lr_mult / (1 - beta1^k) * m / (sqrt(v) / sqrt(1 - beta2^k) + eps),   lr_k = lr gamma^(k-1);   shadow = bf16(p), nearest even.
+ *   1 - beta^k, gamma^(k-1) and the step size are formed in float64 by one thread on the device, from the doubles of VlgAdamHyper.
+ * VlgOptTensor: param / exp_avg / exp_avg_sq float32 [numel] (4-byte aligned, nothing more), shadow bf16 [numel] or NULL (2-byte aligned).
+ * vlg_adam_clip_plan validates such a table ON THE HOST (no HIP call); the caller then copies the array to the device ONCE and hands that copy
+ * to every step as `table` -- the gradients' addresses, new at every eager step, travel by value in the launch arguments.
+ * state: 32 bytes of device memory, 8-byte aligned, the caller's: int64 count of updates done @0, float32 lr @8 (the caller may overwrite it
+ * between updates), and of the last update float32 pre-clip norm @12, coef @16, lr_k @20.  The kernels advance the count (a replayed HIP
+ * graph takes a new step number at every replay); no host synchronisation, no copy.
+ * vlg_adam_clip_step: numel [count] on the HOST (the table's element counts: they size the launches), grads [count] device pointers,
+ *   grad_dtypes [count] VLG_F32 / VLG_BF16 (aligned to their element), ws of vlg_adam_clip_workspace(numel, count) bytes (8-byte aligned;
+ *   its contents need not survive between calls).  Two launches per 128 tensors: all squared-sum launches, then all update launches;
+ *   partial sums in fixed slots added in a fixed order, no atomics: the same inputs give the same bits.  count == 0: nothing to do. */
+typedef struct VlgOptTensor {
+    void* param;
+    float *exp_avg, *exp_avg_sq;
+    void* shadow;
+    long long numel;
+    float lr_mult, weight_decay;
+} VlgOptTensor;
+typedef struct VlgAdamHyper {
+    double beta1, beta2, eps, gamma, max_norm;
+} VlgAdamHyper;
+int vlg_adam_clip_plan(const VlgOptTensor* items, int count);
+size_t vlg_adam_clip_workspace(const long long* numel, int count);
+int vlg_adam_clip_step(const VlgOptTensor* table, const long long* numel, const void* const* grads, const int* grad_dtypes, int count,
+                       const VlgAdamHyper* hyper, void* state, void* ws, size_t ws_bytes, void* stream);
+
 /* Device self-test of the cross-lane (DPP / ds_swizzle) exchange primitives the DP kernels rely on.
  * `scratch` = one device int; after the stream drains it holds 0 iff the primitives behave as assumed. */
 int vlg_selftest_xlane(int* scratch, void* stream);
@@ -690,7 +725,7 @@ int vlg_selftest_xlane(int* scratch, void* stream);
 /* Thread-local message for the last non-zero return on this thread ("" if none). */
 const char* vlg_last_error(void);
 
-/* Library / ABI version, e.g. 142 = 0.1.4.2 (145: vlg_eval_metrics, vlg_eval_metrics_workspace and vlg_deptree_mbr_decode added later under the same number -- no existing argument list changed; 145: vlg_step_batch_prepare and vlg_grounding_loss_ntok added; round 6, 142: vlg_attn_fuse / vlg_attn_fuse_backward take key_chunk and a workspace -- the key-split form for the
+/* Library / ABI version, e.g. 142 = 0.1.4.2 (145: vlg_adam_clip_plan / _workspace / _step added under the same number -- no existing argument list changed; 145: vlg_eval_metrics, vlg_eval_metrics_workspace and vlg_deptree_mbr_decode added later under the same number -- no existing argument list changed; 145: vlg_step_batch_prepare and vlg_grounding_loss_ntok added; round 6, 142: vlg_attn_fuse / vlg_attn_fuse_backward take key_chunk and a workspace -- the key-split form for the
  * shipped 1369-key factor layout -- and the gradients' storage type; vlg_attn_fuse_workspace added; round 5, 141: vlg_dropout, vlg_rng_advance, vlg_vis_encoder(_backward) added, vlg_linear_wgrad takes ld_dw and in_dtype;
  * the Python binding refuses a library whose version differs from the one it was written against; round 4: vlg_langfeat_* take the activations' storage type and the SharedDropout masks,
  * vlg_langfeat_rowscale, vlg_ff_* added, vlg_ndmv_potentials* take row strides and the gradients' storage type; round 3, 120: vlg_linear_wgrad, vlg_langfeat_*, vlg_ndmv_potentials*, vlg_dmv1o_viterbi added;

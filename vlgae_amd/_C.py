@@ -41,6 +41,17 @@ class WgradPartial(ctypes.Structure):
                 + [(n, ctypes.c_int) for n in ("ld_dy", "ld_x", "K", "M", "N", "in_dtype", "want_bias", "want_x_colsum")])
 
 
+class OptTensor(ctypes.Structure):
+    """VlgOptTensor of include/vlgae_amd.h: one row of the optimiser's table (vlg_adam_clip_plan / vlg_adam_clip_step)."""
+    _fields_ = ([(n, ctypes.c_void_p) for n in ("param", "exp_avg", "exp_avg_sq", "shadow")] + [("numel", ctypes.c_longlong), ("lr_mult", ctypes.c_float),
+                ("weight_decay", ctypes.c_float)])
+
+
+class AdamHyper(ctypes.Structure):
+    """VlgAdamHyper of include/vlgae_amd.h."""
+    _fields_ = [(n, ctypes.c_double) for n in ("beta1", "beta2", "eps", "gamma", "max_norm")]
+
+
 # symbol -> (restype, argtypes); one entry per declaration in include/vlgae_amd.h
 SIGNATURES = {
     "vlg_dmv1o_inside": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
@@ -134,6 +145,9 @@ SIGNATURES = {
     "vlg_feed_batches": (_i, [_vp, ctypes.c_int64, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "vlg_feed_npy_shape": (_i, [ctypes.c_char_p, _vp, _vp]),
     "vlg_feed_collate_npy": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i]),
+    "vlg_adam_clip_plan": (_i, [_vp, _i]),
+    "vlg_adam_clip_workspace": (_sz, [_vp, _i]),
+    "vlg_adam_clip_step": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "vlg_selftest_xlane": (_i, [_vp, _vp]),
     "vlg_last_error": (ctypes.c_char_p, []),
     "vlg_version": (_i, []),

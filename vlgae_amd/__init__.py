@@ -7,6 +7,7 @@ Sub-modules
     scorer         score construction feeding the DP (factorised-bilinear scores -> merged potentials)
     parser_ff      the parser's feed-forwards in front of it (head_ff / mid_ff / scorer projections)
     eval_step      one evaluation step (eval-mode forward, decode, loss, metric update) without a host synchronisation
+    optim          the optimiser step between two training steps: global-norm clip + Adam + lr decay + bf16 refresh, two launches
     metrics        UAS / UCM, factor -> image and box / relation accuracy as device counters (the reference's metric classes)
     rules1o        the gold tree's rule counts, score and adjoint (the parser's rule-supervised initialisation epochs)
     vis_encoder    the visual encoder's pairwise relation features
