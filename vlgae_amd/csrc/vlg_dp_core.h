@@ -626,113 +626,171 @@ VLG_HD void dmv_bw_span(const DmvCtx& c, int w, int G, int D, bool live, int rr,
 // barrier like everything else and cost no wait of their own -- and stay in registers across the barrier: behind it only the
 // adjoint reads are requested, and the exponentials of the weights run while those are in flight.  Same operations on the same
 // operands in the same order per result: bit-identical counts (tools/time_headline.py's SHA-256).
+//
+// Addressing (round 8).  In this image a lane keeps its span slot for a whole segment, so with D = slot (P + 1) and rr its split-point
+// residue every cell it touches at width w is a lane constant plus w times a stride that is uniform over the wavefront:
+//                                    DIR 0 (left)                      DIR 1 (right)
+//   own slot kO (C, I, gCc, gCi, gI) D + wP            [P cells / w]   D + w + 1           [1]
+//   tape cell kS (S)                 D + wP            [P]             D + w               [1]
+//   same-width partner (su)          D                 [0]             D + wP + w + 1      [P + 1]
+//   column walk (uu, gCc)            D + rr P          [0]             D + rr P + P + w + 1  [1]     term u: + u G P
+//   row walk (vv, gI)                D + wP + rr       [P]             D + rr + 2          [0]     term u: + u G
+//   xa, its gCi word                 D + rr + 1        [0]             D + rr + 1          [0]     term u: + u G
+//   xb, its gCi word                 D + wP + rr + 1   [P]             D + wP + rr + 1     [P]     term u: + u G
+// BwAddr holds one byte address per (chart, row of this table) with the chart's start and the component's offset folded in, built once
+// per segment; a width moves the moving ones by one add of a scalar each (the stride is chosen by direction once per segment), the
+// terms of a lane are compile-time offsets u G 8 (the column walk: one add of the scalar G P cell size per further term), and the
+// direction never reaches the width loop.  X::pin hides from the device's compiler that an address is "LDS base + offset": it would
+// carry the offset and add the base back in front of every access.  (What hipcc makes of the steps: addresses that share a stride
+// share ONE scalar counter, added to the pinned address where it is used -- the same count of vector adds, fewer registers.)  The
+// value addresses run one width ahead of the adjoint addresses: the reads that width w's body issues for width w - 1 use the cells
+// whose adjoint twins body w - 1 then reads.
+// A lane that has no span at any width of the segment shadows span 0; one that gets its span later in the segment addresses it from
+// the start, so until then its (unused) reads fall on rows past Ne: inside twice the chart's cells, never stored through.  Like the
+// out-of-range split points of NOCLAMP, they need memory that can be read: LDS on the device, the arena plus slack in the host driver.
 template <int TM>
 struct BwVals {
     float2 oc, sv, vv[TM];
     float Sv, su, uu[TM], xa[TM], xb[TM];
 };
 
-template <int DIRT, int TM, bool NOCLAMP>
-VLG_HD void dmv_bw_load_vals(const DmvCtx& c, int w, int G, int D, int rr, BwVals<TM>& v, int dir_rt) {
-    const int DIR = DIRT < 0 ? dir_rt : DIRT;
-    const int P = c.P, DW = D + VLG_MUL24(w, P);
-    const float* Cf = reinterpret_cast<const float*>(c.C);
-    const int eA = 2 * (D + 1) + (DIR == 0 ? 1 : 0), eB = 2 * (DW + 1) + (DIR == 0 ? 0 : 1);
-    const int eU = DIR == 0 ? D : D + P + w + 1, eV = DIR == 0 ? DW : D + 2;
-    const int kO = DIR == 0 ? DW : D + w + 1, kS = DIR == 0 ? DW : D + w;
-    const int selfr = DIR == 0 ? 0 : w - 1;
-    v.oc = c.C[kO];
-    v.Sv = c.S[kS];
-    v.su = Cf[2 * (eU + VLG_MUL24(selfr, P)) + 1];
-    v.sv = c.I[eV + selfr];
+template <typename T>
+VLG_HD T bw_ld(const char* p, int off = 0) { return *reinterpret_cast<const T*>(p + off); }
+template <typename T>
+VLG_HD void bw_st(char* p, int off, T v) { *reinterpret_cast<T*>(p + off) = v; }
+
+struct BwAddr {
+    const char *vC, *vI, *vS, *vSU, *vUU, *vVV, *vXA, *vXB;   // value charts: own C / I cell, tape cell, partner, the four walks
+    char *aGc, *aGi, *aI, *aUU, *aVV, *aXA, *aXB;             // adjoint charts: own gCc / gCi / gI cell, the four walks
+    int sO8, sO4, sSU, sUU8, sUU4, sVV, sXB;                  // byte strides per width (descending: all <= 0), wave-uniform
+    int gp8, gp4;                                             // column-walk stride between a lane's terms: G P cells of 8 / 4 bytes
+    VLG_HDM void step_vals() { vC += sO8; vI += sO8; vS += sO4; vSU += sSU; vUU += sUU8; vVV += sVV; vXB += sXB; }
+    VLG_HDM void step_adj() { aGc += sO4; aGi += sO8; aI += sO8; aUU += sUU4; aVV += sVV; aXB += sXB; }
+};
+
+// addresses of the span at D (lane residue rr) at width w, direction `right`, for both the value and the adjoint charts
+template <int G, typename X>
+VLG_HD BwAddr dmv_bw_addr(const DmvCtx& c, int w, int D, int rr, bool right, X& x) {
+    const int P = c.P, DW = D + VLG_MUL24(w, P), q = D + rr, qP = D + VLG_MUL24(rr, P);
+    const int kO = right ? D + w + 1 : DW, kS = right ? D + w : DW;
+    const int iSU = right ? DW + w + 1 : D, iUU = right ? qP + P + w + 1 : qP, iVV = right ? q + 2 : DW + rr;
+    const int iXA = q + 1, iXB = DW + rr + 1;
+    const int cA = right ? 0 : 4, cB = right ? 4 : 0;   // component of xa / xb: CR(i, .) .NC for SL, .HC for SR; CL(j, .) the other one
+    const char *C = reinterpret_cast<const char*>(c.C), *I = reinterpret_cast<const char*>(c.I), *S = reinterpret_cast<const char*>(c.S);
+    char *gCc = reinterpret_cast<char*>(c.gCc), *gCi = reinterpret_cast<char*>(c.gCi), *gI = reinterpret_cast<char*>(c.gI);
+    BwAddr a;
+    a.vC = x.pin(C + 8 * kO);
+    a.vI = x.pin(I + 8 * kO);
+    a.vS = x.pin(S + 4 * kS);
+    a.vSU = x.pin(C + 8 * iSU + 4);
+    a.vUU = x.pin(C + 8 * iUU + 4);
+    a.vVV = x.pin(I + 8 * iVV);
+    a.vXA = x.pin(C + 8 * iXA + cA);
+    a.vXB = x.pin(C + 8 * iXB + cB);
+    a.aGc = x.pin(gCc + 4 * kO);
+    a.aGi = x.pin(gCi + 8 * kO);
+    a.aI = x.pin(gI + 8 * kO);
+    a.aUU = x.pin(gCc + 4 * iUU);
+    a.aVV = x.pin(gI + 8 * iVV);
+    a.aXA = x.pin(gCi + 8 * iXA + cA);
+    a.aXB = x.pin(gCi + 8 * iXB + cB);
+    a.sO8 = x.uniform(right ? -8 : -8 * P);
+    a.sO4 = x.uniform(right ? -4 : -4 * P);
+    a.sSU = x.uniform(right ? -8 * (P + 1) : 0);
+    a.sUU8 = x.uniform(right ? -8 : 0);
+    a.sUU4 = x.uniform(right ? -4 : 0);
+    a.sVV = x.uniform(right ? 0 : -8 * P);
+    a.sXB = -8 * P;
+    a.gp8 = 8 * G * P;
+    a.gp4 = 4 * G * P;
+    return a;
+}
+
+// the value reads of one width: the own cells and TM terms
+template <int G, int TM>
+VLG_HD void dmv_bw_load_vals(const BwAddr& a, BwVals<TM>& v) {
+    v.oc = bw_ld<float2>(a.vC);
+    v.Sv = bw_ld<float>(a.vS);
+    v.su = bw_ld<float>(a.vSU);
+    v.sv = bw_ld<float2>(a.vI);
 #pragma unroll
     for (int u = 0; u < TM; ++u) {
-        const int r = rr + u * G, rc = NOCLAMP ? r : (r < w ? r : w - 1), rP = VLG_MUL24(rc, P);
-        v.uu[u] = Cf[2 * (eU + rP) + 1];
-        v.vv[u] = c.I[eV + rc];
-        v.xa[u] = Cf[eA + 2 * rc];
-        v.xb[u] = Cf[eB + 2 * rc];
+        v.uu[u] = bw_ld<float>(a.vUU, u * a.gp8);
+        v.vv[u] = bw_ld<float2>(a.vVV, u * G * 8);
+        v.xa[u] = bw_ld<float>(a.vXA, u * G * 8);
+        v.xb[u] = bw_ld<float>(a.vXB, u * G * 8);
     }
 }
 
-// dmv_bw_span (TU > 0, one chunk) on prefetched values `v`; with `more`, `nxt` receives the values of width wn for the span at Dn
-template <int SR, int DIRT, int TU, int TM, typename X, bool NOCLAMP>
-VLG_HD void dmv_bw_span_p(const DmvCtx& c, int w, int G, int D, bool live, int rr, X& x, const BwVals<TM>& v, BwVals<TM>& nxt, bool more,
-                          int wn, int Dn, int dir_rt) {
-    const int DIR = DIRT < 0 ? dir_rt : DIRT;
-    const int P = c.P, DW = D + VLG_MUL24(w, P);
-    float* gCif = reinterpret_cast<float*>(c.gCi);
-    const int eA = 2 * (D + 1) + (DIR == 0 ? 1 : 0), eB = 2 * (DW + 1) + (DIR == 0 ? 0 : 1);
-    const int eU = DIR == 0 ? D : D + P + w + 1, eV = DIR == 0 ? DW : D + 2;
-    const int kO = DIR == 0 ? DW : D + w + 1, kS = DIR == 0 ? DW : D + w;
-    const int selfr = DIR == 0 ? 0 : w - 1;
-    // ---- adjoint reads: what the barrier was for ----
-    const float ga = c.gCc[kO];
-    const float2 gb = c.gCi[kO];
-    const float2 gi_old = c.gI[kO];
-    int b0 = 0, b1 = 0, bs = 0;
-    if (SR == VLG_SR_MAX) { b0 = c.bpC[kO * 2]; b1 = c.bpC[kO * 2 + 1]; bs = c.bpS[kS]; }
-    float o_c[TU], o_ga[TU], o_gb[TU];
-    float2 o_gi[TU];
+// One span of width w on the prefetched values `v` (Log semiring: the Max semiring's outside pass is the back-pointer walk), in two
+// halves with the refill of `v` between them (dmv_bw_segment_p).  BwAdj is what the first half hands to the second: the adjoint cells
+// it has requested and the weights' factors.  Both halves run the segment's TM terms at every width: a term past the width's last
+// split point (r >= w; widths 9 ... 16 and 3, 4 of a 40-word sentence have one) reads cells nobody uses and stores nothing -- its
+// store branch is skipped by the whole wavefront -- where one body per term count T <= TM made the outside pass twice the code, and
+// the bodies' different register assignments met in moves at the loop's end.
+template <int TM>
+struct BwAdj {
+    float ga, o_c[TM], o_ga[TM], o_gb[TM];
+    float2 gb, gi_old, o_gi[TM];
+    float e0[TM], e1[TM], es[TM], s0, s1;   // factors 2^min(t - out, 0) of the terms of CL | CR (.x, .y) and SL | SR, and of the same-width term
+};
+
+// first half: the adjoint reads -- what the barrier was for -- and, while they are in flight, the weights' exponentials from registers
+// (adj_w = g * 2^min(t - out, 0): the factor first)
+template <int G, int TM, typename X>
+VLG_HD void dmv_bw_span_p1(const BwAddr& a, X& x, const BwVals<TM>& v, BwAdj<TM>& s) {
+    s.ga = bw_ld<float>(a.aGc);
+    s.gb = bw_ld<float2>(a.aGi);
+    s.gi_old = bw_ld<float2>(a.aI);
 #pragma unroll
-    for (int u = 0; u < TU; ++u) {
-        const int r = rr + u * G, rc = NOCLAMP ? r : (r < w ? r : w - 1), rP = VLG_MUL24(rc, P);
-        o_gi[u] = c.gI[eV + rc];
-        o_c[u] = c.gCc[eU + rP];
-        o_ga[u] = gCif[eA + 2 * rc];
-        o_gb[u] = gCif[eB + 2 * rc];
+    for (int u = 0; u < TM; ++u) {
+        s.o_gi[u] = bw_ld<float2>(a.aVV, u * G * 8);
+        s.o_c[u] = bw_ld<float>(a.aUU, u * a.gp4);
+        s.o_ga[u] = bw_ld<float>(a.aXA, u * G * 8);
+        s.o_gb[u] = bw_ld<float>(a.aXB, u * G * 8);
     }
-    // ---- the weights' exponentials, from registers, while those reads are in flight (adj_w = g * 2^min(t - out, 0): the factor first) ----
-    float e0[TU], e1[TU], es[TU], s0 = 0.f, s1 = 0.f;
-    if (SR != VLG_SR_MAX) {
 #pragma unroll
-        for (int u = 0; u < TU; ++u) {
-            e0[u] = VLG_EXP(fminf(v.uu[u] + v.vv[u].x - v.oc.x, 0.f));
-            e1[u] = VLG_EXP(fminf(v.uu[u] + v.vv[u].y - v.oc.y, 0.f));
-            es[u] = VLG_EXP(fminf(v.xa[u] + v.xb[u] - v.Sv, 0.f));
-        }
-        s0 = VLG_EXP(fminf(v.su + v.sv.x - v.oc.x, 0.f));
-        s1 = VLG_EXP(fminf(v.su + v.sv.y - v.oc.y, 0.f));
+    for (int u = 0; u < TM; ++u) {
+        s.e0[u] = VLG_EXP(fminf(v.uu[u] + v.vv[u].x - v.oc.x, 0.f));
+        s.e1[u] = VLG_EXP(fminf(v.uu[u] + v.vv[u].y - v.oc.y, 0.f));
+        s.es[u] = VLG_EXP(fminf(v.xa[u] + v.xb[u] - v.Sv, 0.f));
     }
+    s.s0 = VLG_EXP(fminf(v.su + v.sv.x - v.oc.x, 0.f));
+    s.s1 = VLG_EXP(fminf(v.su + v.sv.y - v.oc.y, 0.f));
+    // X::settle: the factors are computed HERE, so `v` is dead behind this point and its registers can take the next width's values
+    // (left to itself the compiler sinks the exponentials into the store branches, behind the refill, and pays with a copy of the set)
+#pragma unroll
+    for (int u = 0; u < TM; ++u) {
+        x.settle(s.e0[u]);
+        x.settle(s.e1[u]);
+        x.settle(s.es[u]);
+    }
+    x.settle(s.s0);
+    x.settle(s.s1);
+}
+
+// second half: the weights and the read-modify-writes.  gc_ok: the span is live and not the masked root cell; selfr: the split point
+// whose incomplete span has this same width.
+template <int G, int TM, typename X>
+VLG_HD void dmv_bw_span_p2(const BwAddr& a, int w, bool live, bool gc_ok, int rr, int selfr, X& x, const BwAdj<TM>& s) {
     float2 gc = make_float2(0.f, 0.f);                        // total adjoint of CL(j,i) | CR(i,j)
-    if (live && !(DIR == 1 && D == 0 && w != c.len)) gc = make_float2(gb.x, ga + gb.y);   // masked root cell: dmv.py:63
-    float w0[TU], w1[TU], self[2];
-#pragma unroll
-    for (int u = 0; u < TU; ++u) {
-        const int r = rr + u * G;
-        const bool ok = r < w;
-        if (SR == VLG_SR_MAX) {
-            w0[u] = ok ? adj_w<SR>(gc.x, 0.f, 0.f, r, b0) : 0.f;
-            w1[u] = ok ? adj_w<SR>(gc.y, 0.f, 0.f, r, b1) : 0.f;
-        } else {
-            w0[u] = ok ? gc.x * e0[u] : 0.f;
-            w1[u] = ok ? gc.y * e1[u] : 0.f;
-        }
-    }
-    if (SR == VLG_SR_MAX) {
-        self[0] = adj_w<SR>(gc.x, 0.f, 0.f, selfr, b0);
-        self[1] = adj_w<SR>(gc.y, 0.f, 0.f, selfr, b1);
-    } else {
-        self[0] = gc.x * s0;
-        self[1] = gc.y * s1;
-    }
-    // ---- the next width's value reads: ahead of this width's stores ----
-    if (more) dmv_bw_load_vals<DIRT, TM, NOCLAMP>(c, wn, G, Dn, rr, nxt, dir_rt);
+    if (gc_ok) gc = make_float2(s.gb.x, s.ga + s.gb.y);       // (zero for a dead lane and for the masked root cell, dmv.py:63)
+    const float self0 = gc.x * s.s0, self1 = gc.y * s.s1;
     x.lockstep();   // the lanes of a group sit in one wavefront: every load above precedes every store below
-    const float2 gi = make_float2(gi_old.x + self[0], gi_old.y + self[1]);   // complete adjoint of IL(j,i) | IR(i,j)
+    const float2 gi = make_float2(s.gi_old.x + self0, s.gi_old.y + self1);   // complete adjoint of IL(j,i) | IR(i,j)
     const float gs = gi.x + gi.y;
 #pragma unroll
-    for (int u = 0; u < TU; ++u) {
+    for (int u = 0; u < TM; ++u) {
         const int r = rr + u * G;
         if (live && r < w) {
-            const float ws = SR == VLG_SR_MAX ? adj_w<SR>(gs, 0.f, 0.f, r, bs) : gs * es[u];
-            if (r != selfr) c.gI[eV + r] = make_float2(o_gi[u].x + w0[u], o_gi[u].y + w1[u]);
-            c.gCc[eU + VLG_MUL24(r, P)] = o_c[u] + (w0[u] + w1[u]);
-            gCif[eA + 2 * r] = o_ga[u] + ws;
-            gCif[eB + 2 * r] = o_gb[u] + ws;
+            const float w0 = gc.x * s.e0[u], w1 = gc.y * s.e1[u], ws = gs * s.es[u];
+            if (r != selfr) bw_st(a.aVV, u * G * 8, make_float2(s.o_gi[u].x + w0, s.o_gi[u].y + w1));
+            bw_st(a.aUU, u * a.gp4, s.o_c[u] + (w0 + w1));
+            bw_st(a.aXA, u * G * 8, s.o_ga[u] + ws);
+            bw_st(a.aXB, u * G * 8, s.o_gb[u] + ws);
         }
     }
-    if (live && rr == 0) c.gI[kO] = gi;   // == d logZ / d attach[j,i,:] | attach[i,j,:]
+    if (live && rr == 0) bw_st(a.aI, 0, gi);   // == d logZ / d attach[j,i,:] | attach[i,j,:]
 }
 
 // widths w1-1 ... w0 of one segment of the short-sentence image (one span per lane group and width: (Ne - w) G <= the lanes of a direction)
@@ -740,38 +798,35 @@ template <int SR, int LG, typename X>
 VLG_HD void dmv_bw_segment_p(const DmvCtx& c, int w0, int w1, int tid, int nt, X& x) {
     constexpr int G = 1 << LG;
     constexpr int TM = short_tmax(LG, kShortN, VLG_DP_LANES_BW);
-    constexpr bool NC = X::kChartsInLds;
+    if constexpr (SR == VLG_SR_MAX) return;   // never run: the Max semiring's outside pass is the back-pointer walk (dmv_run)
     if (w1 <= w0) return;
     const int nd = nt >> 1;
     const bool right = x.uniform(tid >= nd);
-    const int dir = right ? 1 : 0;
     const int t = dir_lane<VLG_MIRROR_RIGHT>(tid, nd, right);
     const int rr = t & (G - 1), slot = t >> LG, wslot = (t & ~63) >> LG;   // wslot: the first span of this lane's wavefront
-    const int Ds = VLG_MUL24(slot, c.P + 1);
-    BwVals<TM> va, vb;   // ping-pong: the body of one width reads one and fills the other (no copies)
-    {
-        const int spans = c.Ne - (w1 - 1);
-        dmv_bw_load_vals<-1, TM, NC>(c, w1 - 1, G, slot < spans ? Ds : 0, rr, va, dir);
-    }
-    auto one_width = [&](int w, const BwVals<TM>& cur, BwVals<TM>& nxt) {
-        const int spans = c.Ne - w;
+    const int D = slot < c.Ne - w0 ? VLG_MUL24(slot, c.P + 1) : 0;         // no span at any width of the segment: shadow span 0
+    const int gc_hi = right && slot == 0 ? 1 : c.Ne;                       // CR(0, w): zero unless w == len, the width with ONE span (dmv.py:63)
+    BwAddr a = dmv_bw_addr<G>(c, w1 - 1, D, rr, right, x);
+    // ONE register set of values and ONE place in the loop that refills it, for every wavefront: behind the last use of this width's
+    // values (the first half of the body), ahead of this width's stores (the second half).  No copies of the set.  At a segment's
+    // last width the refill reads the cells of width w0 - 1 >= 0 for nothing (the next segment, with its own group size, loads its
+    // own): a branch around it brings moves back, the set it skips and the set it loads meeting in a merge.
+    BwVals<TM> v;
+    dmv_bw_load_vals<G, TM>(a, v);
+    a.step_vals();
+    for (int w = w1 - 1; w >= w0; --w) {
+        const int spans = x.uniform(c.Ne - w), selfr = x.uniform(right ? w - 1 : 0);   // (pinned to scalar registers, and the loop counter with them)
         const bool live = slot < spans;
-        const int D = live ? Ds : 0;
-        const bool more = w > w0;
-        const int Dn = slot < spans + 1 ? Ds : 0;   // the span of width w - 1 (one more span than this width has)
-        const int T = (w + G - 1) >> LG;
-        if (X::kSkipDeadWaves && wslot >= spans) {   // (wave-uniform) no span of this width in this wavefront: only the prefetch
-            if (more) dmv_bw_load_vals<-1, TM, NC>(c, w - 1, G, Dn, rr, nxt, dir);
-        } else if (TM == 1 || T == 1) dmv_bw_span_p<SR, -1, 1, TM, X, NC>(c, w, G, D, live, rr, x, cur, nxt, more, w - 1, Dn, dir);
-        else if (TM == 2 || T == 2) dmv_bw_span_p<SR, -1, 2, TM, X, NC>(c, w, G, D, live, rr, x, cur, nxt, more, w - 1, Dn, dir);
-        else dmv_bw_span_p<SR, -1, 3, TM, X, NC>(c, w, G, D, live, rr, x, cur, nxt, more, w - 1, Dn, dir);
+        const bool body = !(X::kSkipDeadWaves && wslot >= spans);   // (wave-uniform) a wavefront without a span of this width: only the refill
+        BwAdj<TM> s;
+        if (body) dmv_bw_span_p1<G, TM>(a, x, v, s);
+        dmv_bw_load_vals<G, TM>(a, v);
+        if (body) dmv_bw_span_p2<G, TM>(a, w, live, live && spans <= gc_hi, rr, selfr, x, s);
+        a.step_vals();
+        a.step_adj();
         VLG_WSTAMP(x, 1, w, 0);
         x.sync();
         VLG_WSTAMP(x, 1, w, 1);
-    };
-    for (int w = w1 - 1; w >= w0; w -= 2) {
-        one_width(w, va, vb);
-        if (w - 1 >= w0) one_width(w - 1, vb, va);
     }
 }
 

@@ -166,6 +166,17 @@ struct DevX {
     // a value the caller knows to be wave-uniform: pin it to an SGPR so that branches on it are scalar branches
     __device__ __forceinline__ bool uniform(bool v) { return __builtin_amdgcn_readfirstlane((int)v) != 0; }
     __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+    // An LDS address that is to stay whole in one VGPR (the short image's per-segment addresses, vlg_dp_core.h: BwAddr): behind the
+    // empty asm the compiler no longer knows it as "dynamic LDS base + offset", so it cannot carry the offset alone and add the base
+    // back in front of every access.  Only for pointers into LDS (the short image is placement 0: every chart).
+    template <typename T>
+    __device__ __forceinline__ T* pin(T* p) {
+        auto q = (__attribute__((address_space(3))) T*)p;
+        asm("" : "+v"(q));
+        return (T*)q;
+    }
+    // a value that is to be computed at this point of the program, not later where it is used
+    __device__ __forceinline__ void settle(float& v) { asm volatile("" : "+v"(v)); }
 #ifdef VLG_STAMP
     // per-width stamps (VLG_WSTAMP in the segment loops): wst = this workgroup's LDS table [pass][w][k][wave] of the low 32 bits of
     // s_memtime, k = 0 when the wave has finished its body of width w, k = 1 when the barrier behind it has released the wave
