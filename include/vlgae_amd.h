@@ -47,7 +47,8 @@ enum {
     VLG_ERR_SHAPE = 0x1001,     /* mirrors the reference's shape asserts (deptree.py:149,154) */
     VLG_ERR_DTYPE = 0x1002,
     VLG_ERR_ARG = 0x1003,
-    VLG_ERR_WORKSPACE = 0x1004
+    VLG_ERR_WORKSPACE = 0x1004,
+    VLG_ERR_NULL = 0x1005       /* vlg_deptree_sample: a required buffer is NULL, or not exactly one of rng / u is given */
 };
 
 /* DMV1oStruct._dp through _Struct.sum -- src/model/torch_struct/dmv.py:19-66, helpers.py:101-116
@@ -92,6 +93,22 @@ int vlg_dmv1o_decode(const void* dec, const void* attach, const int64_t* lengths
 /* Same for the projective CRF; with `arc` = arc marginals this is the MBR decode of ldndmv.py:294-299. */
 int vlg_deptree_decode(const void* arc, const int64_t* lengths, int B, int N, int in_dtype, float* best_score,
                        int64_t* heads, void* ws, size_t ws_bytes, void* stream);
+
+/* Draw S trees per sentence from the projective CRF, on the device: `StructDistribution.sample` (distributions.py:195-217) as head
+ * vectors, one launch.  The Log-semiring inside pass of vlg_deptree_inside runs once per workgroup; then every wavefront walks whole
+ * samples top-down from CR(0,len), drawing each split from the inside charts (rule, cell keys and LDS budget: DESIGN.md section 2, "Drawing trees").
+ *   The uniform of cell (kind, lo, hi) of sample s of sentence b depends on nothing else.  Exactly one source is given:
+ *     u   [S,B,3,N,N] float32, read at [s,b,kind,lo,hi] (common random numbers, antithetic draws, tests), or
+ *     rng the device-resident (seed, step) pair of vlg_dropout / vlg_rng_advance: Philox4x32-10 with `site` mixed into the key as
+ *         vlg_dropout does, counter (kind << 16 | hi << 8 | lo, s, b, low word of step), u = (first word >> 8) * 2^-24.
+ *   heads [S,B,N] int64 as vlg_deptree_decode writes them (0 for c = 0 and padding); logp [S,B] (optional) = score of the sampled
+ *   tree on the input potentials - logZ; logZ [B] (optional).  An invalid length gives heads 0, logp NaN, logZ NaN.
+ *   The launch is a (B, Y) grid, Y = vlg_deptree_sample_blocks(B, N, S) (>= 1; every block repeats the inside pass and takes a share
+ *   of the samples; the result does not depend on Y); ws holds vlg_workspace_bytes(VLG_OP_DEPTREE_INSIDE, B * Y, N, 0) bytes.
+ *   VLG_ERR_NULL unless exactly one of rng / u is non-NULL (and for NULL arc / heads); VLG_ERR_SHAPE for S < 1. */
+int vlg_deptree_sample(const void* arc, const int64_t* lengths, int B, int N, int in_dtype, int S, const uint64_t* rng, unsigned site,
+                       const float* u, int64_t* heads, float* logp, float* logZ, void* ws, size_t ws_bytes, void* stream);
+int vlg_deptree_sample_blocks(int B, int N, int S);
 
 /* The MBR decode of ldndmv.py:294-299 straight from the DMV1o arc marginals: DependencyCRF(marginals.sum(-1)).argmax.  marginals
  * [B,N,N,2] float32 (head, child, valence), as vlg_dmv1o_inside_outside / vlg_dmv1o_marginals_viterbi write grad_attach; the valence sum
@@ -362,7 +379,7 @@ int vlg_linear_wgrad_partial_group(const VlgWgradPartial* items, int count, void
  *     mask != NULL: explicit fp32 values [rows, cols] -- or, shared_rows > 0, one [cols] row per `shared_rows` consecutive rows
  *                   (SharedDropout, nn/dropout.py:42-63, `shared_dropout` of the encoder's config);
  *     rng  != NULL: a counter-based draw, Philox4x32-10 keyed by the DEVICE-resident pair rng[0] = seed, rng[1] = step over the element
- *                   index (`site` is added to the seed: one state serves every dropout layer of a step with independent streams) -- nothing is stored, the adjoint regenerates the same bits, and a HIP-graph replay sees the step that
+ *                   index (`site`, times an odd constant, is XORed into the key's second word -- never added to the seed: one state serves every dropout layer of a step with independent streams, and (seed, site) pairs do not alias) -- nothing is stored, the adjoint regenerates the same bits, and a HIP-graph replay sees the step that
  *                   vlg_rng_advance (a one-thread launch: rng[1] += 1) left there.  p is applied in steps of 2^-16.
  *   x (`dtype`), add / out (`out_dtype`; add NULL = none: the other producer of a gradient that has two), cols a multiple of 8,
  *   buffers 16-byte aligned.
@@ -725,7 +742,7 @@ int vlg_selftest_xlane(int* scratch, void* stream);
 /* Thread-local message for the last non-zero return on this thread ("" if none). */
 const char* vlg_last_error(void);
 
-/* Library / ABI version, e.g. 142 = 0.1.4.2 (145: vlg_adam_clip_plan / _workspace / _step added under the same number -- no existing argument list changed; 145: vlg_eval_metrics, vlg_eval_metrics_workspace and vlg_deptree_mbr_decode added later under the same number -- no existing argument list changed; 145: vlg_step_batch_prepare and vlg_grounding_loss_ntok added; round 6, 142: vlg_attn_fuse / vlg_attn_fuse_backward take key_chunk and a workspace -- the key-split form for the
+/* Library / ABI version, e.g. 142 = 0.1.4.2 (145: vlg_deptree_sample, vlg_deptree_sample_blocks and VLG_ERR_NULL added under the same number -- no existing argument list changed; 145: vlg_adam_clip_plan / _workspace / _step added under the same number -- no existing argument list changed; 145: vlg_eval_metrics, vlg_eval_metrics_workspace and vlg_deptree_mbr_decode added later under the same number -- no existing argument list changed; 145: vlg_step_batch_prepare and vlg_grounding_loss_ntok added; round 6, 142: vlg_attn_fuse / vlg_attn_fuse_backward take key_chunk and a workspace -- the key-split form for the
  * shipped 1369-key factor layout -- and the gradients' storage type; vlg_attn_fuse_workspace added; round 5, 141: vlg_dropout, vlg_rng_advance, vlg_vis_encoder(_backward) added, vlg_linear_wgrad takes ld_dw and in_dtype;
  * the Python binding refuses a library whose version differs from the one it was written against; round 4: vlg_langfeat_* take the activations' storage type and the SharedDropout masks,
  * vlg_langfeat_rowscale, vlg_ff_* added, vlg_ndmv_potentials* take row strides and the gradients' storage type; round 3, 120: vlg_linear_wgrad, vlg_langfeat_*, vlg_ndmv_potentials*, vlg_dmv1o_viterbi added;

@@ -61,6 +61,8 @@ SIGNATURES = {
     "vlg_dmv1o_decode": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "vlg_deptree_decode": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "vlg_deptree_mbr_decode": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "vlg_deptree_sample": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, ctypes.c_uint, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "vlg_deptree_sample_blocks": (_i, [_i, _i, _i]),
     "vlg_eval_metrics_workspace": (_sz, [_i]),
     "vlg_eval_metrics": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "vlg_dmv1o_marginals_viterbi_supported": (_i, [_i]),

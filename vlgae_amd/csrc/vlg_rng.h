@@ -1,6 +1,8 @@
-// vlg_rng.h -- the counter-based dropout draw shared by the element-wise kernels (vlg_encoders.hip, vlg_ff.hip): Philox4x32-10
-// (Salmon et al., SC'11) keyed by a DEVICE-resident (seed, step) pair, counter = element-group index.  Nothing is stored: the adjoint
-// regenerates the bits of the forward pass, and a replayed HIP graph sees the step that vlg_rng_advance left in device memory.
+// vlg_rng.h -- the counter-based draws of the library: Philox4x32-10 (Salmon et al., SC'11) keyed by a DEVICE-resident (seed, step) pair.
+// Key = (low word of seed, high word of seed XOR site * 0x9E3779B9) for every user (site_key below): the site never enters the seed's
+// arithmetic.  Counter: dropout (keep8: vlg_encoders.hip, vlg_ff.hip) = (element-group index, step), 64 bits each; tree sampling
+// (vlg_sample.hip) = (kind << 16 | hi << 8 | lo, sample, sentence, low word of step).  Nothing is stored: the adjoint regenerates the
+// bits of the forward pass, and a replayed HIP graph sees the step that vlg_rng_advance left in device memory.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -21,15 +23,19 @@ __device__ __forceinline__ uint4 philox4x32_10(uint4 ctr, uint2 key) {
     return ctr;
 }
 
+// The Philox key of one drawing site (a dropout layer, a sampling call) under `seed`.  The site goes into the key's second word on its own
+// (times an odd constant), NOT into the seed's arithmetic: with `seed + site` the stream of (seed s, site 2) was that of (seed s + 1,
+// site 1) -- a trainer seeding its ranks with seed + rank would have drawn rank 0's mid_ff mask and rank 1's text-encoder mask from the
+// same bits.
+__device__ __forceinline__ uint2 site_key(uint64_t seed, uint32_t site) {
+    return make_uint2((uint32_t)seed, (uint32_t)(seed >> 32) ^ (site * 0x9E3779B9u));
+}
+
 // keep flags of eight consecutive elements (group index g): 16 random bits each, keep <=> bits >= thr, thr = round(p * 65536);
 // m[k] = `scale` where kept, 0 where dropped.  `site`: which dropout layer of the step draws (independent streams off one state).
 __device__ __forceinline__ void keep8(const uint64_t* __restrict__ rng, uint32_t site, uint64_t g, uint32_t thr, float scale, float (&m)[8]) {
-    // The site goes into the key's second word on its own (times an odd constant), NOT into the seed's arithmetic: with `seed + site` the
-    // stream of (seed s, site 2) was that of (seed s + 1, site 1) -- a trainer seeding its ranks with seed + rank would have drawn rank 0's
-    // mid_ff mask and rank 1's text-encoder mask from the same bits.
     const uint64_t seed = rng[0], step = rng[1];
-    const uint4 r = philox4x32_10(make_uint4((uint32_t)g, (uint32_t)(g >> 32), (uint32_t)step, (uint32_t)(step >> 32)),
-                                  make_uint2((uint32_t)seed, (uint32_t)(seed >> 32) ^ (site * 0x9E3779B9u)));
+    const uint4 r = philox4x32_10(make_uint4((uint32_t)g, (uint32_t)(g >> 32), (uint32_t)step, (uint32_t)(step >> 32)), site_key(seed, site));
     const uint32_t w[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {

@@ -19,7 +19,8 @@ from .semirings import NEGINF, LogSemiring, MaxSemiring
 def _out_of_scope(name):
     raise NotImplementedError(
         f"StructDistribution.{name}: no caller in VLGAE uses it (only partition / max / argmax / marginals are "
-        "reached; SURVEY.md section 2) -- outside the MI355X hot path this package implements.")
+        "reached; SURVEY.md section 2) -- outside the MI355X hot path this package implements.  (Drawing trees is "
+        "implemented for DependencyCRF as `sample_heads` / `heads_to_parts`.)")
 
 
 class StructDistribution(Distribution):
@@ -216,6 +217,41 @@ class DependencyCRF(StructDistribution):
     def argmax_heads(self):
         "Extension: best tree as heads [B,N] on the device (see DMV1o.argmax_heads; MBR decode of ldndmv.py:294-303)."
         return F.deptree_decode(self.log_potentials, self.lengths)[1]
+
+    def sample_heads(self, n, rng=None, u=None, return_log_prob=False):
+        """Extension (not in the reference): n trees per sentence drawn from the distribution, as heads [n,B,N] int64 on the device
+        (heads[s,b,c] = head of word c, 0 for c = 0 and padding) -- one kernel launch, no host synchronisation.  `rng`: an
+        `encoders.DeviceRng` whose (seed, step) keys the draws (the same state gives the same trees; the caller advances it);
+        `u`: explicit uniforms [n,B,3,N,N] instead.  With neither, the distribution creates and keeps a DeviceRng seeded from
+        `torch.initial_seed()` and advances it after each call.  return_log_prob=True: (heads, log_prob [n,B]).
+        The reference's `sample(sample_shape)` (distributions.py:195-217) stays out of scope under that name -- it raises, as every
+        other unreached method does; `DependencyCRF.heads_to_parts(dist.sample_heads(n))` is its event format."""
+        own = rng is None and u is None
+        if own:
+            if getattr(self, "_sample_rng", None) is None:
+                from ..encoders import DeviceRng
+                self._sample_rng = DeviceRng(torch.initial_seed() & 0x7FFFFFFFFFFFFFFF, self.log_potentials.device)
+            rng = self._sample_rng
+        heads, logp, _ = F.deptree_sample(self.log_potentials, self.lengths, n, rng=rng, u=u, want_logp=return_log_prob)
+        if own:
+            rng.advance()
+        return (heads, logp) if return_log_prob else heads
+
+    @staticmethod
+    def heads_to_parts(heads, lengths=None):
+        """Extension: head vectors [..., B, N] -> 0/1 float32 arc indicators [..., B, N, N] (parts[..., h, c] = 1 iff h is the head of
+        word c, 1 <= c <= length; lengths None = N - 1) on the heads' device: the event format of the reference's `sample` /
+        `to_parts` (deptree.py:163-186), which `log_prob` accepts."""
+        N = heads.shape[-1]
+        pos = torch.arange(N, device=heads.device)
+        if lengths is None:
+            word = (pos >= 1).expand(heads.shape)
+        else:
+            ln = torch.as_tensor(lengths, device=heads.device).to(torch.int64)
+            word = (pos >= 1) & (pos <= ln.unsqueeze(-1))
+            word = word.expand(heads.shape)
+        parts = torch.zeros(heads.shape + (N,), dtype=torch.float32, device=heads.device)
+        return parts.scatter_(-2, heads.unsqueeze(-2), word.to(torch.float32).unsqueeze(-2))
 
     def log_prob(self, value):
         "log p(tree) for 0/1 arc indicators `value` [..., B, N, N] (distributions.py:55-75)."

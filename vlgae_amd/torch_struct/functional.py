@@ -226,6 +226,37 @@ def deptree_decode(arc, lengths=None):
     return best, heads
 
 
+def deptree_sample(arc, lengths, n, rng=None, site=0, u=None, want_logp=True):
+    """n trees per sentence drawn from the projective CRF of arc scores [B,N,N], in ONE launch (vlg_deptree_sample):
+    (heads [n,B,N] int64 as deptree_decode writes them, logp [n,B] float32 or None, logZ [B]).  The uniforms come either from
+    `rng` (an encoders.DeviceRng: Philox draws off its device-resident (seed, step), `site` as for the dropout layers) or from the explicit
+    table `u` [n,B,3,N,N] float32, read at [s,b,kind,lo,hi] (common random numbers, antithetic draws); exactly one of the two."""
+    _C.require_gpu(arc, "deptree_sample")
+    if arc.dim() != 3:
+        raise ValueError("potentials must have dim of 3 (unlabeled)")
+    B, N, N2 = arc.shape
+    assert N == N2, "Non-square potentials"
+    n = int(n)
+    dt, arc_c = _C.in_dtype(arc)
+    lengths = _lengths(lengths, B, arc.device, allow_none=True)
+    if (rng is None) == (u is None):
+        raise ValueError("deptree_sample: pass exactly one of rng and u")
+    if u is not None:
+        if tuple(u.shape) != (n, B, 3, N, N) or u.dtype != torch.float32 or u.device != arc.device:
+            raise ValueError(f"deptree_sample: u must be float32 [n,B,3,N,N] = {(n, B, 3, N, N)} on {arc.device}")
+        u = u.contiguous()
+    heads = torch.empty((n, B, N), dtype=torch.int64, device=arc.device)
+    logp = torch.empty((n, B), dtype=torch.float32, device=arc.device) if want_logp else None
+    logZ = torch.empty(B, dtype=torch.float32, device=arc.device)
+    L = _C.lib()
+    blocks = L.vlg_deptree_sample_blocks(B, N, n) if B > 0 and n > 0 else 1
+    ws, nb = _workspace(_C.OP_DEPTREE_INSIDE, B * blocks, N, _C.SEMIRING_LOG, arc.device)
+    _C.check(L.vlg_deptree_sample(_C.ptr(arc_c), _C.ptr(lengths), B, N, dt, n, None if rng is None else _C.ptr(rng.state), int(site),
+                                  _C.ptr(u), _C.ptr(heads), _C.ptr(logp), _C.ptr(logZ), _C.ptr(ws), nb, _C.stream_of(arc)),
+             "deptree_sample")
+    return heads, logp, logZ
+
+
 def deptree_mbr_decode(marginals, lengths=None):
     """The MBR decode of src/model/ldndmv.py:294-299 from the DMV1o arc marginals [B,N,N,2] (float32: `grad_attach` of the Log
     semiring's inside-outside pass): `DependencyCRF(marginals.sum(-1)).argmax` as (best_score [B], heads [B,N] int64) in ONE DepTree
