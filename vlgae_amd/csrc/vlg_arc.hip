@@ -154,6 +154,7 @@ __global__ __launch_bounds__(64 * kTriWaves) void tri_kernel(const typename Mfma
 // before.  The x range is split over `xs` workgroups (6 at M = 10 496: 246 workgroups); their partial sums go to separate slabs that
 // a second launch adds in a fixed order (bit-reproducible; two-addend atomics when the caller has no workspace).
 constexpr int kTri2Threads = 512, kTri2Rows = 256;
+constexpr int kTri2MaxXPer = 96;   // x values per workgroup: their [x][256] float32 factors fit behind the two weight planes (64 KB + 96 KB = the 160 KB of LDS)
 
 __global__ __launch_bounds__(kTri2Threads) void tri2_kernel(const uint16_t* __restrict__ c, const uint16_t* __restrict__ w,
                                                             const uint16_t* __restrict__ p, int M, int X, int xs,
@@ -275,11 +276,12 @@ static int tri2_splits(int M, int X) {   // ~one workgroup per CU
     int xs = (256 + n_rb / 2) / n_rb;
     xs = xs < 1 ? 1 : (xs > 8 ? 8 : xs);
     while (xs > 1 && X / xs < 8) --xs;
+    while ((X + xs - 1) / xs > kTri2MaxXPer) ++xs;   // (many row blocks and a long x range: more ranges than the CU count asks for)
     return xs;
 }
 static size_t tri2_part_bytes(int M, int X) { const int xs = tri2_splits(M, X); return xs > 1 ? sizeof(float) * (size_t)xs * M * 128 : 0; }
 
-// part: xs slabs of [M][128] floats (fixed-order sum into out), or null: two ranges met by atomicAdd in a zeroed out
+// part: xs slabs of [M][128] floats (fixed-order sum into out), or null: two ranges met by atomicAdd in a zeroed out (X <= 2 kTri2MaxXPer)
 static int launch_tri2(const void* c, const void* w, const void* p, int M, int X, float* out, float* part, hipStream_t s) {
     const int xs = part ? tri2_splits(M, X) : 2;
     const int n_rb = (M + kTri2Rows - 1) / kTri2Rows;
@@ -597,7 +599,7 @@ static int dispatch_tri(const void* c, const void* w, const void* p, int M, int 
         if (rc) return rc;
     } else {
         int rc;
-        if (tri2_applies(M, X, H, Y, false)) rc = launch_tri2(c, w, p, M, X, out, part, s);
+        if (tri2_applies(M, X, H, Y, false) && (part || (X + 1) / 2 <= kTri2MaxXPer)) rc = launch_tri2(c, w, p, M, X, out, part, s);
         else if (Y == 128) rc = launch_tri<false, 4>(c, w, p, M, X, H, out, s);
         else if (Y == 64) rc = launch_tri<false, 2>(c, w, p, M, X, H, out, s);
         else if (Y == 32) rc = launch_tri<false, 1>(c, w, p, M, X, H, out, s);
