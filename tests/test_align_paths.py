@@ -378,7 +378,7 @@ def test_constants_read_from_the_sources():
     assert num(r"kAMWaves = (\d+),") == K_AM_WAVES and num(r"kAMRows = (\d+),") == K_AM_ROWS
     assert num(r"struct MfmaCfg<false> \{[^}]*?RTB = (\d+)", m) == RTB["bf16"] and num(r"struct MfmaCfg<true> \{[^}]*?RTB = (\d+)", m) == RTB["f32"]
     assert num(r"#define VLG_AF_RT (\d+)") == AF_RT
-    assert num(r"align_max_kernel<(\d+)>\), grid") == AM_RT
+    assert num(r"align_max_kernel<(\d+)>, grid") == AM_RT
     # the shared_full bound and divisibility, the shared_max and tile48 bounds (as expressions of the constants above)
     assert tuple(map(int, num(r"!out_maxV && !out_maxQ && !out_diag && V <= (\d+) && V % (\d+) == 0\)"))) == (SHARED_FULL_MAX_V, 4)
     assert len(re.findall(r"!f32in && d == 128 && !out_full && \(out_maxV \|\| out_maxQ\) && V <= kAMRows\)", s)) == 1

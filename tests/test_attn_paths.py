@@ -602,7 +602,13 @@ def test_constants_read_from_the_source():
     assert int(one(r"constexpr int kAttnMaxFT = (\d+);")) == MAX_FT
     assert int(one(r"constexpr int kStagePitch = (\d+);")) * 64 == STAGE_BYTES and one(r"constexpr int kStageBytes = (.*?);") == "2 * 32 * kStagePitch"
     assert int(one(r"constexpr int kSweepPitch = (\d+);")) * 64 == SWEEP_BYTES and one(r"constexpr int kSweepBytes = (.*?);") == "64 * kSweepPitch"
-    assert one(r"sizeof\(float\) \* \(tile_f \+ per_q \* QC\) > (\d+) \* 1024\) QC >>= 1;") == "150" and one(r"if \(lds > (\d+) \* 1024\) \{") == "60"
+    assert one(r"sizeof\(float\) \* \(tile_f \+ per_q \* QC\) > (\d+) \* 1024\) QC >>= 1;") == "150"
+    # the generic kernel goes through vlg::launch like every other, whose one threshold for raising the dynamic-LDS limit is the HIP default:
+    # the 60 KiB the restatement still marks (GEN_ATTR_ABOVE) lies below it, so both rows about it launch without the attribute call
+    launch_h = open(os.path.join(ROOT, "vlgae_amd", "csrc", "vlg_launch.h")).read()
+    assert re.findall(r"constexpr size_t kDefaultDynamicLds = (\d+) \* 1024;", launch_h) == ["64"] and len(re.findall(r"if \(lds > kDefaultDynamicLds\) \{", launch_h)) == 1
+    assert len(re.findall(r'launch\("attn_fuse_kernel", attn_fuse_kernel<INV>, dim3\(\(L \+ QC - 1\) / QC, B\), dim3\(kAlignThreads\), lds, s,', s)) == 1
+    assert GEN_ATTR_ABOVE < 64 * 1024 and "hipFuncSetAttribute" not in s
     assert one(r"cost = \(double\)\(\(w \+ 1023\) / 1024\) \* cand \* ([\d.]+) \+ \(double\)w \* ([\d.]+);") == ("2.0", "0.008")
     assert one(r"return \(size_t\)\(h >> 4\) \* (\d+) \+ (\d+); \}") == ("256", "32")
     assert one(r"T = V > (\d+) \? 4 : \(V \+ 15\) / 16;") == "48" and one(r"switch \(V > (\d+) \? 4 : \(V \+ 15\) / 16\)") == "48"

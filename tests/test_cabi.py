@@ -46,6 +46,17 @@ def test_native_sources_read_no_environment_variable():
     assert not [f for f in sorted(os.listdir(csrc)) if "getenv" in open(os.path.join(csrc, f)).read()]
 
 
+def test_kernel_launches_go_through_one_helper():
+    # vlg::launch (vlg_launch.h) is the only place that raises a kernel's dynamic-LDS limit or launches one
+    csrc = os.path.join(ROOT, "vlgae_amd", "csrc")
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc))}
+    users = {tok: [f for f in text if tok in text[f]] for tok in ("hipFuncSetAttribute", "hipLaunchKernelGGL", "<<<")}
+    assert all(files in ([], ["vlg_launch.h"]) for files in users.values()), users
+    assert sorted({f for files in users.values() for f in files}) == ["vlg_launch.h"], users
+    assert users["hipFuncSetAttribute"] == ["vlg_launch.h"], users
+    assert not [f for f in text if "static bool attr_set" in text[f]]
+
+
 def test_version_and_error_plumbing(lib):
     from vlgae_amd import _C
     assert lib.vlg_version() >= 100

@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "vlg_common.h"
+#include "vlg_launch.h"
 #include "vlg_dp_core.h"   // F32In / BF16In element loaders
 #include "vlg_ground.h"
 #include "vlg_mfma.h"
@@ -1349,11 +1350,8 @@ static int launch_align_full(const void* txt, const void* vis, const uint8_t* tm
     if (a_per_block > A) a_per_block = A;
     dim3 grid((A + a_per_block - 1) / a_per_block, by);
     const size_t lds = sizeof(float) * (size_t)kAMWaves * (VLG_AF_RT * 16) * V;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(align_full_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return set_error((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(align_full_kernel, grid, dim3(kAMThreads), lds, s, (const uint16_t*)txt, (const uint16_t*)vis, tmask, vmask, B, A, Q, V,
-                       neg_inf, out_full, a_per_block);
-    return check_launch("align_full_kernel");
+    return launch("align_full_kernel", align_full_kernel, grid, dim3(kAMThreads), lds, s, (const uint16_t*)txt, (const uint16_t*)vis, tmask, vmask, B, A, Q, V,
+                  neg_inf, out_full, a_per_block);
 }
 
 // ---- float32 features -> two fp16 parts under one power-of-two scale per tensor (round 5; see align_argmax_kernel<NP = 2>) ----
@@ -1411,9 +1409,11 @@ static int launch_align_argmax_f32(const void* txt, const void* vis, const uint8
     uint16_t *tl = th + n0, *vh = tl + n0, *vl = vh + n1;
     float* part = scratch + (n0 + n1);
     float* inv = part + 2 * kSplitBlocks;
-    hipLaunchKernelGGL(align_absmax_kernel, dim3(kSplitBlocks, 2), dim3(256), 0, s, (const float*)txt, n0, (const float*)vis, n1, part);
-    hipLaunchKernelGGL(align_split_kernel, dim3(256, 2), dim3(256), 0, s, (const float*)txt, n0, (const float*)vis, n1, part, th, tl, vh, vl, inv);
-    if (int rc = check_launch("align_split_kernel")) return rc;
+    if (int rc = launch("align_absmax_kernel", align_absmax_kernel, dim3(kSplitBlocks, 2), dim3(256), 0, s, (const float*)txt, n0, (const float*)vis, n1, part))
+        return rc;
+    if (int rc = launch("align_split_kernel", align_split_kernel, dim3(256, 2), dim3(256), 0, s, (const float*)txt, n0, (const float*)vis, n1, part, th, tl, vh,
+                        vl, inv))
+        return rc;
     const AlignParts parts{tl, vl, inv};
     const int by = (B + kAMWaves - 1) / kAMWaves;
     const int ng = (V + kAMRows - 1) / kAMRows;
@@ -1421,21 +1421,16 @@ static int launch_align_argmax_f32(const void* txt, const void* vis, const uint8
     if (a_per_block < (8 + ng - 1) / ng) a_per_block = (8 + ng - 1) / ng;
     if (a_per_block > A) a_per_block = A;
     dim3 grid((A + a_per_block - 1) / a_per_block, by);
-#define VLG_AAM2(HQ, MU)                                                                                                      \
-    hipLaunchKernelGGL((align_argmax_kernel<HQ, true, MU, 2>), grid, dim3(kAMThreads), 0, s, th, vh, tmask, vmask, B, A, Q, V, neg_inf, out_maxV, \
-                       out_maxQ, a_per_block, xa, parts)
-    if (out_maxQ) { if (ng > 1) VLG_AAM2(true, true); else VLG_AAM2(true, false); }
-    else { if (ng > 1) VLG_AAM2(false, true); else VLG_AAM2(false, false); }
-#undef VLG_AAM2
-    if (int rc = check_launch("align_argmax_kernel (fp16 parts)")) return rc;
+    auto k = out_maxQ ? (ng > 1 ? align_argmax_kernel<true, true, true, 2> : align_argmax_kernel<true, true, false, 2>)
+                      : (ng > 1 ? align_argmax_kernel<false, true, true, 2> : align_argmax_kernel<false, true, false, 2>);
+    if (int rc = launch("align_argmax_kernel (fp16 parts)", k, grid, dim3(kAMThreads), 0, s, th, vh, tmask, vmask, B, A, Q, V, neg_inf, out_maxV, out_maxQ,
+                        a_per_block, xa, parts))
+        return rc;
     if (xa.pen) {
         const int pd_nw = ng >= 4 ? 4 : 1;
         const size_t pd_lds = sizeof(float) * ((size_t)pd_nw * kPdRT * 16 * kPdP + (size_t)pd_nw * 256);
-        hipError_t pe = hipFuncSetAttribute(reinterpret_cast<const void*>(align_prior_diag_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pd_lds);
-        if (pe != hipSuccess) return set_error((int)pe, "hipFuncSetAttribute: %s", hipGetErrorString(pe));
-        hipLaunchKernelGGL(align_prior_diag_kernel<2>, dim3(std::min(A, B)), dim3(64 * pd_nw), pd_lds, s, th, vh, tmask, vmask, B, A, Q, V, neg_inf, out_maxV,
-                           out_maxQ, xa, parts);
-        return check_launch("align_prior_diag_kernel (fp16 parts)");
+        return launch("align_prior_diag_kernel (fp16 parts)", align_prior_diag_kernel<2>, dim3(std::min(A, B)), dim3(64 * pd_nw), pd_lds, s, th, vh, tmask,
+                      vmask, B, A, Q, V, neg_inf, out_maxV, out_maxQ, xa, parts);
     }
     return 0;
 }
@@ -1455,32 +1450,24 @@ static int launch_align_max(const void* txt, const void* vis, const uint8_t* tma
     // positions wanted: both products on the matrix cores (172 vs 267 us at config-2).  The maxima alone stay with align_max_kernel:
     // without the searches that one is not vector-ALU bound, and the second product only costs (ARGS = false measured: 149 vs 130 us)
     if constexpr (ARGS) {
-        if (out_maxQ)
-#define VLG_AAM(HQ, MU)                                                                                                       \
-    hipLaunchKernelGGL((align_argmax_kernel<HQ, true, MU>), grid, dim3(kAMThreads), 0, s, (const uint16_t*)txt, (const uint16_t*)vis, tmask, \
-                       vmask, B, A, Q, V, neg_inf, out_maxV, out_maxQ, a_per_block, xa, AlignParts{nullptr, nullptr, nullptr})
-            { if (ng > 1) VLG_AAM(true, true); else VLG_AAM(true, false); }
-        else
-            { if (ng > 1) VLG_AAM(false, true); else VLG_AAM(false, false); }
-#undef VLG_AAM
+        auto k = out_maxQ ? (ng > 1 ? align_argmax_kernel<true, true, true> : align_argmax_kernel<true, true, false>)
+                          : (ng > 1 ? align_argmax_kernel<false, true, true> : align_argmax_kernel<false, true, false>);
+        if (int rc = launch("align_argmax_kernel", k, grid, dim3(kAMThreads), 0, s, (const uint16_t*)txt, (const uint16_t*)vis, tmask, vmask, B, A, Q, V,
+                            neg_inf, out_maxV, out_maxQ, a_per_block, xa, AlignParts{nullptr, nullptr, nullptr}))
+            return rc;
         if (xa.pen) {
-            if (int rc = check_launch("align_argmax_kernel")) return rc;
             // wavefronts per diagonal pair: the region groups of a many-column image are dealt round.  Eight (round 6: 157 KB of score
             // tiles, the whole LDS of a CU) for the shipped layout's 29 groups: there are only B workgroups, the kernel is a chain of
             // dependent rounds, and 4 rounds instead of 8 took it from 162 to ~90 us at B = 64
             const int pd_nw = ng >= 8 ? 8 : ng >= 4 ? 4 : 1;
             const size_t pd_lds = sizeof(float) * ((size_t)pd_nw * kPdRT * 16 * kPdP + (size_t)pd_nw * 256);
-            hipError_t pe = hipFuncSetAttribute(reinterpret_cast<const void*>(align_prior_diag_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pd_lds);
-            if (pe != hipSuccess) return set_error((int)pe, "hipFuncSetAttribute: %s", hipGetErrorString(pe));
-            hipLaunchKernelGGL(align_prior_diag_kernel<1>, dim3(std::min(A, B)), dim3(64 * pd_nw), pd_lds, s, (const uint16_t*)txt, (const uint16_t*)vis,
-                               tmask, vmask, B, A, Q, V, neg_inf, out_maxV, out_maxQ, xa, AlignParts{nullptr, nullptr, nullptr});
-            return check_launch("align_prior_diag_kernel");
+            return launch("align_prior_diag_kernel", align_prior_diag_kernel<1>, dim3(std::min(A, B)), dim3(64 * pd_nw), pd_lds, s, (const uint16_t*)txt,
+                          (const uint16_t*)vis, tmask, vmask, B, A, Q, V, neg_inf, out_maxV, out_maxQ, xa, AlignParts{nullptr, nullptr, nullptr});
         }
-        return check_launch("align_argmax_kernel");
+        return 0;
     } else {
-        hipLaunchKernelGGL((align_max_kernel<6>), grid, dim3(kAMThreads), 0, s, (const uint16_t*)txt, (const uint16_t*)vis, tmask, vmask, B, A, Q, V,
-                           neg_inf, out_maxV, out_maxQ, a_per_block);
-        return check_launch("align_max_kernel");
+        return launch("align_max_kernel", align_max_kernel<6>, grid, dim3(kAMThreads), 0, s, (const uint16_t*)txt, (const uint16_t*)vis, tmask, vmask, B, A, Q,
+                      V, neg_inf, out_maxV, out_maxQ, a_per_block);
     }
 }
 
@@ -1626,15 +1613,8 @@ static int launch_align_mfma(const void* txt, const void* vis, const uint8_t* tm
     dim3 grid(diag_only ? std::max(1, std::min((n_grp + 3) / 4, 16)) : (A + 4 * a_per_wave - 1) / (4 * a_per_wave), B);
     constexpr int QB = RTBV * 16;
     const size_t lds = TILE ? sizeof(float) * 4 * (size_t)(QB * kTileVP + 2 * QB) : 0;
-    auto k = align_mfma_kernel<F32IN, KCH, TILE, ARGS, RTBV, DIRECT>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds);
-        if (e != hipSuccess) return set_error((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    }
-    hipLaunchKernelGGL(k, grid, dim3(kAlignThreads), lds, s, (const typename C::T*)txt, (const typename C::T*)vis, tmask,
-                       vmask, B, A, Q, V, neg_inf, out_full, out_maxV, out_maxQ, out_diag, a_per_wave, xa);
-    return check_launch("align_mfma_kernel");
+    return launch("align_mfma_kernel", align_mfma_kernel<F32IN, KCH, TILE, ARGS, RTBV, DIRECT>, grid, dim3(kAlignThreads), lds, s, (const typename C::T*)txt,
+                  (const typename C::T*)vis, tmask, vmask, B, A, Q, V, neg_inf, out_full, out_maxV, out_maxQ, out_diag, a_per_wave, xa);
 }
 
 // =====================================================================================================
@@ -2040,6 +2020,39 @@ __global__ __launch_bounds__(384 * NF) __attribute__((amdgpu_waves_per_eu(3, 4))
     }
 }
 
+// the matrix-core routes of vlg_bilinear_align for one (dtype, d) (the comment there tells them apart)
+template <bool F32, int KCHV>
+static int align_mfma_route(const void* txt, const void* vis, const uint8_t* tmask, const uint8_t* vmask, int B, int A, int Q, int V, float neg_inf,
+                            float* out_full, float* out_maxV, float* out_maxQ, float* out_diag, hipStream_t s) {
+    const bool tile = out_full || out_diag || out_maxV;   // max over Q alone needs no LDS round trip
+    if (tile && !out_full) {
+        if ((out_maxV || out_maxQ) && V <= kCTB * 16)
+            return launch_align_mfma<F32, KCHV, true, false, 3>(txt, vis, tmask, vmask, B, A, Q, V, neg_inf, nullptr, out_maxV, out_maxQ, out_diag, s);
+        if (out_maxV || out_maxQ) {
+            const int rc = launch_align_mfma<F32, KCHV, false, false, MfmaCfg<F32>::RTB, true>(txt, vis, tmask, vmask, B, A, Q, V, neg_inf, nullptr, out_maxV,
+                                                                                             out_maxQ, nullptr, s);
+            if (rc || !out_diag) return rc;
+        }
+        return launch_align_mfma<F32, KCHV, true, false, 3>(txt, vis, tmask, vmask, B, A, Q, V, neg_inf, nullptr, nullptr, nullptr, out_diag, s,
+                                                            AlignArgs{nullptr, nullptr, 0, nullptr, nullptr}, true);
+    }
+    return tile ? launch_align_mfma<F32, KCHV, true>(txt, vis, tmask, vmask, B, A, Q, V, neg_inf, out_full, out_maxV, out_maxQ, out_diag, s)
+                : launch_align_mfma<F32, KCHV, false>(txt, vis, tmask, vmask, B, A, Q, V, neg_inf, out_full, out_maxV, out_maxQ, out_diag, s);
+}
+
+// one image of the split-term adjoint (vlg_bilinear_align_backward): nf fixed indices per workgroup where the image has the two-index form
+template <bool KC, int NKCV, int MTV, int CWV, int NT>
+static int launch_bwd_split(bool f32feat, int nf, int split, size_t lds, hipStream_t s, const float* grad_out, uint16_t* featT, const uint8_t* rm, int fixn,
+                            int O, int M, int K, long so, long sr, long sk, long sfix, int opb, float* out) {
+    // the two-index form where it fits the 168 registers of three waves per SIMD (12-wave blocks)
+    constexpr int NFV = (NKCV == 3 && (MTV == 6 || KC)) ? 1 : 2;
+    const int nfe = nf == 2 ? NFV : 1;
+    auto k = f32feat ? align_bwd_split_f32_kernel<KC, NKCV, MTV, CWV, NT>
+                     : (nfe == 2 ? align_bwd_split_kernel<KC, NKCV, MTV, CWV, NT, NFV> : align_bwd_split_kernel<KC, NKCV, MTV, CWV, NT, 1>);
+    return launch("align_bwd_split_kernel", k, dim3((fixn + nfe - 1) / nfe, split), dim3(64 * MTV * CWV * nfe), lds, s, grad_out, featT, rm, O, M, K, so, sr,
+                  sk, sfix, opb, out, split > 1 ? 1 : 0, fixn);
+}
+
 }  // namespace vlg
 
 extern "C" {
@@ -2060,7 +2073,6 @@ int vlg_bilinear_align(const void* txt, const void* vis, const uint8_t* tmask, c
 
     // ---- matrix-core path: d a whole number of MFMA K-chunks (the model's d = 128; also 64) ----
     const bool f32in = in_dtype == VLG_F32;
-    const bool tile = out_full || out_diag || out_maxV;   // max over Q alone needs no LDS round trip
     // the full tensor is bound by its writes and keeps 96-row passes (bf16).  Fused maxima without the full tensor:
     //   * one region group per image (V <= 48, config-2): the LDS-tile path with 48-row passes (two blocks per CU: 0.274 ->
     //     0.257 ms); keeping max over V in registers instead measured the same or worse there (0.24 ms alone, 0.32 vs 0.28 ms
@@ -2069,23 +2081,6 @@ int vlg_bilinear_align(const void* txt, const void* vis, const uint8_t* tmask, c
     //     and is folded once per image (DIRECT, no LDS: 1.28 -> 0.74 ms at B = 64), the diagonal block comes from a second
     //     launch over the B diagonal pairs;
     //   * the diagonal block alone: only those B pairs are computed (0.187 -> 0.012 ms).
-#define VLG_MFMA(F32, KCHV)                                                                                         \
-    if (tile && !out_full) {                                                                                        \
-        if ((out_maxV || out_maxQ) && V <= kCTB * 16)                                                               \
-            return launch_align_mfma<F32, KCHV, true, false, 3>(txt, vis, tmask, vmask, B, A, Q, V, neg_inf, nullptr, out_maxV, \
-                                                                out_maxQ, out_diag, s);                             \
-        if (out_maxV || out_maxQ) {                                                                                 \
-            const int rc = launch_align_mfma<F32, KCHV, false, false, MfmaCfg<F32>::RTB, true>(                     \
-                txt, vis, tmask, vmask, B, A, Q, V, neg_inf, nullptr, out_maxV, out_maxQ, nullptr, s);              \
-            if (rc || !out_diag) return rc;                                                                         \
-        }                                                                                                           \
-        return launch_align_mfma<F32, KCHV, true, false, 3>(txt, vis, tmask, vmask, B, A, Q, V, neg_inf, nullptr, nullptr,  \
-                                                            nullptr, out_diag, s, AlignArgs{nullptr, nullptr, 0, nullptr, nullptr}, true); \
-    }                                                                                                               \
-    return tile ? launch_align_mfma<F32, KCHV, true>(txt, vis, tmask, vmask, B, A, Q, V, neg_inf, out_full, out_maxV, \
-                                                     out_maxQ, out_diag, s)                                           \
-                : launch_align_mfma<F32, KCHV, false>(txt, vis, tmask, vmask, B, A, Q, V, neg_inf, out_full, out_maxV, \
-                                                      out_maxQ, out_diag, s)
     if (!f32in && d == 128 && !out_full && (out_maxV || out_maxQ) && V <= kAMRows) {
         // fused maxima of one-group images: image tiles shared by eight captions through LDS
         if (int rc = launch_align_max<false>(txt, vis, tmask, vmask, B, A, Q, V, neg_inf, out_maxV, out_maxQ, s)) return rc;
@@ -2096,32 +2091,21 @@ int vlg_bilinear_align(const void* txt, const void* vis, const uint8_t* tmask, c
     // (eight waves' output blocks of 96 x V floats next to the 24 KB image tiles: V <= 44 fits the 160 KB LDS)
     if (!f32in && d == 128 && out_full && !out_maxV && !out_maxQ && !out_diag && V <= 44 && V % 4 == 0)
         return launch_align_full(txt, vis, tmask, vmask, B, A, Q, V, neg_inf, out_full, s);   // stores straight from the accumulators
-    if (!f32in && d == 128) { VLG_MFMA(false, 4); }
-    if (!f32in && d == 64) { VLG_MFMA(false, 2); }
-    if (f32in && d == 128) { VLG_MFMA(true, 8); }
-    if (f32in && d == 64) { VLG_MFMA(true, 4); }
-#undef VLG_MFMA
+    if (!f32in && d == 128) return align_mfma_route<false, 4>(txt, vis, tmask, vmask, B, A, Q, V, neg_inf, out_full, out_maxV, out_maxQ, out_diag, s);
+    if (!f32in && d == 64) return align_mfma_route<false, 2>(txt, vis, tmask, vmask, B, A, Q, V, neg_inf, out_full, out_maxV, out_maxQ, out_diag, s);
+    if (f32in && d == 128) return align_mfma_route<true, 8>(txt, vis, tmask, vmask, B, A, Q, V, neg_inf, out_full, out_maxV, out_maxQ, out_diag, s);
+    if (f32in && d == 64) return align_mfma_route<true, 4>(txt, vis, tmask, vmask, B, A, Q, V, neg_inf, out_full, out_maxV, out_maxQ, out_diag, s);
 
     // ---- generic fp32-FMA path ----
     const size_t lds = sizeof(float) * ((size_t)(kQT + kVT) * (d + 1) + (size_t)kQT * (kVT + 1) + Q + V);
     if (lds > 160 * 1024) return set_error(VLG_ERR_SHAPE, "bilinear_align: d=%d Q=%d V=%d exceed the LDS tile budget", d, Q, V);
     int a_per_block = 8;
     dim3 grid((A + a_per_block - 1) / a_per_block, B);
-#define VLG_LAUNCH(INV)                                                                                            \
-    do {                                                                                                           \
-        auto k = align_kernel<INV>;                                                                                \
-        if (lds > 64 * 1024) {                                                                                     \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),                                   \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);             \
-            if (e != hipSuccess) return set_error((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));        \
-        }                                                                                                          \
-        hipLaunchKernelGGL(k, grid, dim3(kAlignThreads), lds, s, (const INV::T*)txt, (const INV::T*)vis, tmask,    \
-                           vmask, B, A, Q, V, d, neg_inf, out_full, out_maxV, out_maxQ, out_diag, a_per_block);    \
-    } while (0)
-    if (f32in) VLG_LAUNCH(F32In);
-    else VLG_LAUNCH(BF16In);
+#define VLG_LAUNCH(INV)                                                                                                               \
+    launch("align_kernel", align_kernel<INV>, grid, dim3(kAlignThreads), lds, s, (const INV::T*)txt, (const INV::T*)vis, tmask, vmask, B, A, Q, V, d, \
+           neg_inf, out_full, out_maxV, out_maxQ, out_diag, a_per_block)
+    return f32in ? VLG_LAUNCH(F32In) : VLG_LAUNCH(BF16In);
 #undef VLG_LAUNCH
-    return check_launch("align_kernel");
 }
 
 // d = 128, at most 96 rows and 96 contraction positions per pair: the split-term path on the bf16 matrix cores (fp32 features as hi + lo parts).
@@ -2169,12 +2153,11 @@ int vlg_bilinear_align_backward(const float* grad_out, const void* txt, const vo
     auto go_split = [&](const void* feat, const uint8_t* km, const uint8_t* rm, int fixn, int O, int M, int K, long so, long sr,
                         long sk, long sfix, bool kcontig, uint16_t* featT, float* out) -> int {
         const int Kp = (K + 31) / 32 * 32, nkc = Kp / 32;
-        if (f32feat)
-            hipLaunchKernelGGL(align_bwd_transpose_kernel<float>, dim3(O, Kp / 32), dim3(256), 0, s, (const float*)feat, km, K, Kp, featT,
-                               featT + (size_t)O * 128 * Kp);
-        else
-            hipLaunchKernelGGL(align_bwd_transpose_kernel<uint16_t>, dim3(O, Kp / 32), dim3(256), 0, s, (const uint16_t*)feat, km, K, Kp,
-                               featT, (uint16_t*)nullptr);
+        if (int rc = f32feat ? launch("align_bwd_transpose_kernel", align_bwd_transpose_kernel<float>, dim3(O, Kp / 32), dim3(256), 0, s, (const float*)feat, km, K,
+                                      Kp, featT, featT + (size_t)O * 128 * Kp)
+                             : launch("align_bwd_transpose_kernel", align_bwd_transpose_kernel<uint16_t>, dim3(O, Kp / 32), dim3(256), 0, s,
+                                      (const uint16_t*)feat, km, K, Kp, featT, (uint16_t*)nullptr))
+            return rc;
         // bf16 features: two fixed indices per workgroup share each staged feature tile (12 waves, one block per CU)
         const int nf = (!f32feat && fixn >= 64) ? 2 : 1;
         int split = 1;   // the chip covered at least once; two-addend atomics are order-free
@@ -2185,29 +2168,14 @@ int vlg_bilinear_align_backward(const float* grad_out, const void* txt, const vo
             if (e != hipSuccess) return set_error((int)e, "hipMemsetAsync: %s", hipGetErrorString(e));
         }
         const size_t lds = (f32feat ? 4 : 2) * (size_t)128 * (Kp * 2 + 32);
-#define VLG_BS(KC, NKCV, MTV, CWV)                                                                                      \
-        do {                                                                                                            \
-            /* the two-index form where it fits the 168 registers of three waves per SIMD (12-wave blocks) */           \
-            constexpr int NFV = (NKCV == 3 && (MTV == 6 || KC)) ? 1 : 2;                                                \
-            const int nfe = nf == 2 ? NFV : 1;                                                                          \
-            auto k = f32feat ? align_bwd_split_f32_kernel<KC, NKCV, MTV, CWV, kNT>                                      \
-                             : (nfe == 2 ? align_bwd_split_kernel<KC, NKCV, MTV, CWV, kNT, NFV> : align_bwd_split_kernel<KC, NKCV, MTV, CWV, kNT, 1>); \
-            if (lds > 64 * 1024) {                                                                                      \
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-                if (e != hipSuccess) return set_error((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));         \
-            }                                                                                                           \
-            hipLaunchKernelGGL(k, dim3((fixn + nfe - 1) / nfe, split), dim3(64 * MTV * CWV * nfe), lds, s, grad_out, featT, rm, O, M, K, so, \
-                               sr, sk, sfix, opb, out, split > 1 ? 1 : 0, fixn);                                        \
-        } while (0)
-#define VLG_BS2(KC, NKCV)                                                                                               \
-        do { if (M <= 48) VLG_BS(KC, NKCV, 3, kCW3); else VLG_BS(KC, NKCV, 6, 1); } while (0)
-#define VLG_BS3(KC)                                                                                                     \
-        do { if (nkc == 1) VLG_BS2(KC, 1); else if (nkc == 2) VLG_BS2(KC, 2); else VLG_BS2(KC, 3); } while (0)
-        if (kcontig) VLG_BS3(true); else VLG_BS3(false);
+#define VLG_BS(KC, NKCV, MTV, CWV) \
+    launch_bwd_split<KC, NKCV, MTV, CWV, kNT>(f32feat, nf, split, lds, s, grad_out, featT, rm, fixn, O, M, K, so, sr, sk, sfix, opb, out)
+#define VLG_BS2(KC, NKCV) (M <= 48 ? VLG_BS(KC, NKCV, 3, kCW3) : VLG_BS(KC, NKCV, 6, 1))
+#define VLG_BS3(KC) (nkc == 1 ? VLG_BS2(KC, 1) : nkc == 2 ? VLG_BS2(KC, 2) : VLG_BS2(KC, 3))
+        return kcontig ? VLG_BS3(true) : VLG_BS3(false);
 #undef VLG_BS3
 #undef VLG_BS2
 #undef VLG_BS
-        return check_launch("align_bwd_split_kernel");
     };
     auto go = [&](const void* feat, const uint8_t* km, const uint8_t* rm, int fixn, int O, int M, int K, long so, long sr, long sk,
                   long sfix, float* out) -> int {
@@ -2227,26 +2195,16 @@ int vlg_bilinear_align_backward(const float* grad_out, const void* txt, const vo
             if (e != hipSuccess) return set_error((int)e, "hipMemsetAsync: %s", hipGetErrorString(e));
         }
         dim3 grid(gx, fixn, split);
-#define VLG_BWD3(INV, NCTV, NSV)                                                                                       \
-        do {                                                                                                           \
-            auto k = align_bwd_kernel<INV, NCTV, NSV>;                                                                 \
-            if (lds > 64 * 1024) {                                                                                     \
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-                if (e != hipSuccess) return set_error((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));        \
-            }                                                                                                          \
-            hipLaunchKernelGGL(k, grid, dim3(kBwdThreads), lds, s, grad_out, (const INV::T*)feat, km, rm, O, M, K, so, sr, sk,    \
-                               sfix, opb, out, split > 1 ? 1 : 0);                                                     \
-        } while (0)
-#define VLG_BWD(INV, NCTV)                                                                                             \
-        do {                                                                                                           \
-            if (ns == 6) VLG_BWD3(INV, NCTV, 6); else if (ns == 9) VLG_BWD3(INV, NCTV, 9); else if (ns == 12) VLG_BWD3(INV, NCTV, 12); \
-            else if (ns == 21) VLG_BWD3(INV, NCTV, 21); else VLG_BWD3(INV, NCTV, 24);                                  \
-        } while (0)
-        if (in_dtype == VLG_F32) { if (d == 128) VLG_BWD(F32In, 8); else if (d == 64) VLG_BWD(F32In, 4); else VLG_BWD(F32In, 2); }
-        else { if (d == 128) VLG_BWD(BF16In, 8); else if (d == 64) VLG_BWD(BF16In, 4); else VLG_BWD(BF16In, 2); }
+#define VLG_BWD3(INV, NCTV, NSV)                                                                                                       \
+    launch("align_bwd_kernel", align_bwd_kernel<INV, NCTV, NSV>, grid, dim3(kBwdThreads), lds, s, grad_out, (const INV::T*)feat, km, rm, O, M, K, so, \
+           sr, sk, sfix, opb, out, split > 1 ? 1 : 0)
+#define VLG_BWD(INV, NCTV)                                                                                                  \
+    (ns == 6 ? VLG_BWD3(INV, NCTV, 6) : ns == 9 ? VLG_BWD3(INV, NCTV, 9) : ns == 12 ? VLG_BWD3(INV, NCTV, 12) : ns == 21 ? VLG_BWD3(INV, NCTV, 21) \
+                                                                                                                        : VLG_BWD3(INV, NCTV, 24))
+        if (in_dtype == VLG_F32) return d == 128 ? VLG_BWD(F32In, 8) : d == 64 ? VLG_BWD(F32In, 4) : VLG_BWD(F32In, 2);
+        return d == 128 ? VLG_BWD(BF16In, 8) : d == 64 ? VLG_BWD(BF16In, 4) : VLG_BWD(BF16In, 2);
 #undef VLG_BWD
 #undef VLG_BWD3
-        return check_launch("align_bwd_kernel");
     };
     const long QV = (long)Q * V;
     uint16_t* visT = reinterpret_cast<uint16_t*>(ws);
@@ -2255,8 +2213,9 @@ int vlg_bilinear_align_backward(const float* grad_out, const void* txt, const vo
                                                                             : (f32feat ? 2 : 1) * (size_t)A * 128 * ((V + 31) / 32 * 32));
     if (grad_txt && concat) {   // two images per step, their 2 V <= 96 positions side by side
         const long pitch = (long)bwd_concat_pitch(A, V);
-        hipLaunchKernelGGL(align_bwd_concat_transpose_kernel, dim3((unsigned)((pitch + 31) / 32)), dim3(256), 0, s, (const uint16_t*)vis,
-                           vmask, A * V, pitch, visT);
+        if (int rc = launch("align_bwd_concat_transpose_kernel", align_bwd_concat_transpose_kernel, dim3((unsigned)((pitch + 31) / 32)), dim3(256), 0, s,
+                            (const uint16_t*)vis, vmask, A * V, pitch, visT))
+            return rc;
         const int nf = B >= 64 ? 2 : 1;
         int split = ((long)B * 2 <= 1024 * nf && A >= 16) ? 2 : 1;
         const int opb = ((A + split - 1) / split + 1) & ~1;   // even: a step's tile rows start on 16-byte boundaries of featC
@@ -2265,13 +2224,11 @@ int vlg_bilinear_align_backward(const float* grad_out, const void* txt, const vo
             if (e != hipSuccess) return set_error((int)e, "hipMemsetAsync: %s", hipGetErrorString(e));
         }
         const size_t lds = 2 * (size_t)128 * (96 * 2 + 32);
-#define VLG_BS2K(MTV, CWV, NFV)                                                                                         \
-        hipLaunchKernelGGL((align_bwd_split2_kernel<MTV, CWV, kNT, NFV>), dim3((B + NFV - 1) / NFV, split), dim3(384 * NFV), lds, s, grad_out, \
-                           visT, pitch, tmask, A, Q, V, QV, (long)V, (long)A * QV, opb, grad_txt, split > 1 ? 1 : 0, B)
-        if (Q <= 48) { if (nf == 2) VLG_BS2K(3, 2, 2); else VLG_BS2K(3, 2, 1); }
-        else { if (nf == 2) VLG_BS2K(6, 1, 2); else VLG_BS2K(6, 1, 1); }
+#define VLG_BS2K(MTV, CWV, NFV)                                                                                                                        \
+    launch("align_bwd_split2_kernel", align_bwd_split2_kernel<MTV, CWV, kNT, NFV>, dim3((B + NFV - 1) / NFV, split), dim3(384 * NFV), lds, s, grad_out, visT, \
+           pitch, tmask, A, Q, V, QV, (long)V, (long)A * QV, opb, grad_txt, split > 1 ? 1 : 0, B)
+        if (int rc = Q <= 48 ? (nf == 2 ? VLG_BS2K(3, 2, 2) : VLG_BS2K(3, 2, 1)) : (nf == 2 ? VLG_BS2K(6, 1, 2) : VLG_BS2K(6, 1, 1))) return rc;
 #undef VLG_BS2K
-        if (int rc = check_launch("align_bwd_split2_kernel")) return rc;
     } else if (grad_txt) {   // rows q of caption b; outer a, contraction v:  g[((b A + a) Q + q) V + v]
         const int rc = bwd_split_ok(in_dtype, d, Q, V) ? go_split(vis, vmask, tmask, B, A, Q, V, QV, V, 1, (long)A * QV, true, visT, grad_txt)
                                                        : go(vis, vmask, tmask, B, A, Q, V, QV, V, 1, (long)A * QV, grad_txt);

@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "vlg_common.h"
+#include "vlg_launch.h"
 #include "vlg_mfma.h"
 
 namespace vlg {
@@ -286,18 +287,17 @@ static int launch_tri2(const void* c, const void* w, const void* p, int M, int X
     const int xs = part ? tri2_splits(M, X) : 2;
     const int n_rb = (M + kTri2Rows - 1) / kTri2Rows;
     const size_t lds = 2 * (size_t)128 * 128 * 2 + sizeof(float) * kTri2Rows * ((X + xs - 1) / xs);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(tri2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return set_error((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
     const bool atomic = part == nullptr || xs == 1;
     if (atomic && xs > 1) {
-        e = hipMemsetAsync(out, 0, sizeof(float) * (size_t)M * 128, s);
+        hipError_t e = hipMemsetAsync(out, 0, sizeof(float) * (size_t)M * 128, s);
         if (e != hipSuccess) return set_error((int)e, "hipMemsetAsync: %s", hipGetErrorString(e));
     }
-    hipLaunchKernelGGL(tri2_kernel, dim3(n_rb * xs), dim3(kTri2Threads), lds, s, (const uint16_t*)c, (const uint16_t*)w, (const uint16_t*)p,
-                       M, X, xs, atomic ? out : part, (size_t)M * 128, (atomic && xs > 1) ? 1 : 0);
+    if (int rc = launch("tri2_kernel", tri2_kernel, dim3(n_rb * xs), dim3(kTri2Threads), lds, s, (const uint16_t*)c, (const uint16_t*)w, (const uint16_t*)p, M,
+                        X, xs, atomic ? out : part, (size_t)M * 128, (atomic && xs > 1) ? 1 : 0))
+        return rc;
     if (!atomic) {
         const size_t n = (size_t)M * 128;
-        hipLaunchKernelGGL(tri2_reduce_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, part, xs, n, out);
+        return launch("tri2_reduce_kernel", tri2_reduce_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, part, xs, n, out);
     }
     return 0;
 }
@@ -496,8 +496,8 @@ static size_t tri3_carve(char* base, size_t rows, Tri3Ops* o) {
     }
     return 2 * plane + iv;
 }
-static void launch_split_rows(const float* src, size_t rows, const Tri3Ops& o, hipStream_t s) {
-    hipLaunchKernelGGL(tri_split_rows_kernel, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, s, src, rows, o.hi, o.lo, o.inv);
+static int launch_split_rows(const float* src, size_t rows, const Tri3Ops& o, hipStream_t s) {
+    return launch("tri_split_rows_kernel", tri_split_rows_kernel, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, s, src, rows, o.hi, o.lo, o.inv);
 }
 
 // out[m,h] = sum_x c[m,x] sum_y w[x,h,y] p[m,y] from the split forms of w ([X 128 rows]) and p ([M rows]); part: tri3_part_bytes(M, X)
@@ -505,13 +505,12 @@ static int launch_tri3(const float* c, const Tri3Ops& w, const Tri3Ops& p, int M
     const int xs = tri3_splits(M, X);
     const int n_rb = (M + kTri3Rows - 1) / kTri3Rows;
     const size_t lds = 4 * (size_t)64 * 128 * 2 + sizeof(float) * (2 * 64 + (size_t)kTri3Rows * ((X + xs - 1) / xs));
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(tri3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return set_error((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(tri3_kernel, dim3(n_rb * xs), dim3(kTri3Threads), lds, s, c, w.hi, w.lo, w.inv, p.hi, p.lo, p.inv, M, X, xs, xs > 1 ? part : out,
-                       (size_t)M * 128, 0);
+    if (int rc = launch("tri3_kernel", tri3_kernel, dim3(n_rb * xs), dim3(kTri3Threads), lds, s, c, w.hi, w.lo, w.inv, p.hi, p.lo, p.inv, M, X, xs,
+                        xs > 1 ? part : out, (size_t)M * 128, 0))
+        return rc;
     if (xs > 1) {
         const size_t n = (size_t)M * 128;
-        hipLaunchKernelGGL(tri2_reduce_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, part, xs, n, out);
+        return launch("tri2_reduce_kernel", tri2_reduce_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, part, xs, n, out);
     }
     return 0;
 }
@@ -524,8 +523,8 @@ static int launch_tri3_forward(const void* c, const void* w, const void* p, int 
     Tri3Ops wo, po;
     size_t off = tri3_carve(ws, (size_t)X * 128, &wo);
     off += tri3_carve(ws + off, (size_t)M, &po);
-    launch_split_rows((const float*)w, (size_t)X * 128, wo, s);
-    launch_split_rows((const float*)p, (size_t)M, po, s);
+    if (int rc = launch_split_rows((const float*)w, (size_t)X * 128, wo, s)) return rc;
+    if (int rc = launch_split_rows((const float*)p, (size_t)M, po, s)) return rc;
     return launch_tri3((const float*)c, wo, po, M, X, out, reinterpret_cast<float*>(ws + off), s);
 }
 
@@ -533,19 +532,13 @@ template <bool F32IN, int KCH, int RT>
 static int launch_tri_rt(const void* c, const void* w, const void* p, int M, int X, int H, int xs, float* out, hipStream_t s) {
     using T = typename MfmaCfg<F32IN>::T;
     const size_t lds = sizeof(float) * 16 * RT * ((X + xs - 1) / xs);
-    auto k = tri_kernel<F32IN, KCH, RT>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return set_error((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    }
     if (xs > 1) {
         hipError_t e = hipMemsetAsync(out, 0, sizeof(float) * (size_t)M * H, s);
         if (e != hipSuccess) return set_error((int)e, "hipMemsetAsync: %s", hipGetErrorString(e));
     }
     const int n_rb = (M + 16 * RT - 1) / (16 * RT);
     const int blocks = xs == 2 ? ((n_rb + 3) / 4) * 8 : n_rb * xs;
-    hipLaunchKernelGGL(k, dim3(blocks), dim3(64 * kTriWaves), lds, s, (const T*)c, (const T*)w, (const T*)p, M, X, H, xs, out);
-    return 0;
+    return launch("tri_kernel", tri_kernel<F32IN, KCH, RT>, dim3(blocks), dim3(64 * kTriWaves), lds, s, (const T*)c, (const T*)w, (const T*)p, M, X, H, xs, out);
 }
 
 static int device_cus() {
@@ -590,23 +583,17 @@ static int launch_tri(const void* c, const void* w, const void* p, int M, int X,
 static int dispatch_tri(const void* c, const void* w, const void* p, int M, int X, int H, int Y, bool f32in, float* out,
                         hipStream_t s, float* part = nullptr) {
     if (f32in) {
-        int rc;
-        if (part && tri3_applies(M, X, H, Y)) rc = launch_tri3_forward(c, w, p, M, X, out, reinterpret_cast<char*>(part), s);   // (part: tri3_fwd_bytes)
-        else if (Y == 128) rc = launch_tri<true, 8>(c, w, p, M, X, H, out, s);
-        else if (Y == 64) rc = launch_tri<true, 4>(c, w, p, M, X, H, out, s);
-        else if (Y == 32) rc = launch_tri<true, 2>(c, w, p, M, X, H, out, s);
-        else return set_error(VLG_ERR_SHAPE, "trilinear: contracted dimension %d (supported: 32, 64, 128)", Y);
-        if (rc) return rc;
+        if (part && tri3_applies(M, X, H, Y)) return launch_tri3_forward(c, w, p, M, X, out, reinterpret_cast<char*>(part), s);   // (part: tri3_fwd_bytes)
+        if (Y == 128) return launch_tri<true, 8>(c, w, p, M, X, H, out, s);
+        if (Y == 64) return launch_tri<true, 4>(c, w, p, M, X, H, out, s);
+        if (Y == 32) return launch_tri<true, 2>(c, w, p, M, X, H, out, s);
     } else {
-        int rc;
-        if (tri2_applies(M, X, H, Y, false) && (part || (X + 1) / 2 <= kTri2MaxXPer)) rc = launch_tri2(c, w, p, M, X, out, part, s);
-        else if (Y == 128) rc = launch_tri<false, 4>(c, w, p, M, X, H, out, s);
-        else if (Y == 64) rc = launch_tri<false, 2>(c, w, p, M, X, H, out, s);
-        else if (Y == 32) rc = launch_tri<false, 1>(c, w, p, M, X, H, out, s);
-        else return set_error(VLG_ERR_SHAPE, "trilinear: contracted dimension %d (supported: 32, 64, 128)", Y);
-        if (rc) return rc;
+        if (tri2_applies(M, X, H, Y, false) && (part || (X + 1) / 2 <= kTri2MaxXPer)) return launch_tri2(c, w, p, M, X, out, part, s);
+        if (Y == 128) return launch_tri<false, 4>(c, w, p, M, X, H, out, s);
+        if (Y == 64) return launch_tri<false, 2>(c, w, p, M, X, H, out, s);
+        if (Y == 32) return launch_tri<false, 1>(c, w, p, M, X, H, out, s);
     }
-    return check_launch("tri_kernel");
+    return set_error(VLG_ERR_SHAPE, "trilinear: contracted dimension %d (supported: 32, 64, 128)", Y);
 }
 
 // ---- helpers for the adjoint ----------------------------------------------------------------------------------------
@@ -1118,30 +1105,30 @@ static int run_tri_backward_f16x3(const float* child, const float* w, const floa
     tri3_carve(ws + q.off_wB, (size_t)X * Y, &wBo);
     tri3_carve(ws + q.off_g, (size_t)M, &go);
     if (d_child || d_parent) {
-        hipLaunchKernelGGL((tri_permute2_kernel<float>), dim3(X, (Y + 31) / 32), dim3(256), 0, s, w, wA, wB, X, H, Y);
-        launch_split_rows(g, (size_t)M, go, s);
+        if (int rc = launch("tri_permute2_kernel", tri_permute2_kernel<float>, dim3(X, (Y + 31) / 32), dim3(256), 0, s, w, wA, wB, X, H, Y)) return rc;
+        if (int rc = launch_split_rows(g, (size_t)M, go, s)) return rc;
     }
     if (d_child) {   // roles (c, w, p) := (parent, wA [Y][X][H], g)
-        launch_split_rows(wA, (size_t)Y * X, wAo, s);
+        if (int rc = launch_split_rows(wA, (size_t)Y * X, wAo, s)) return rc;
         if (int rc = launch_tri3(parent, wAo, go, M, Y, d_child, part, s)) return rc;
     }
     if (d_parent) {  // roles (c, w, p) := (child, wB [X][Y][H], g)
-        launch_split_rows(wB, (size_t)X * Y, wBo, s);
+        if (int rc = launch_split_rows(wB, (size_t)X * Y, wBo, s)) return rc;
         if (int rc = launch_tri3(child, wBo, go, M, X, d_parent, part, s)) return rc;
     }
     if (d_w) {
         float* maxes = reinterpret_cast<float*>(ws + q.off_max);
-        hipLaunchKernelGGL(tri_absmax3_kernel, dim3(kDw3MaxBlocks), dim3(256), 0, s, child, g, parent, (size_t)M * 128 / 4, maxes);
+        if (int rc = launch("tri_absmax3_kernel", tri_absmax3_kernel, dim3(kDw3MaxBlocks), dim3(256), 0, s, child, g, parent, (size_t)M * 128 / 4, maxes))
+            return rc;
         const int S = dw3_splits(M, X);
         const int KC = ((M + S - 1) / S + kDw3Stage - 1) / kDw3Stage * kDw3Stage;
         const size_t lds = 2 * (size_t)2 * (kDw3XB + 1) * kDw3Stage * kDw3Pitch;   // 108 KB
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(tri_dw3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return set_error((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        hipLaunchKernelGGL(tri_dw3_kernel, dim3((X / kDw3XB) * S), dim3(kDw3Threads), lds, s, child, g, parent, maxes, M, X, KC, S, part);
+        if (int rc = launch("tri_dw3_kernel", tri_dw3_kernel, dim3((X / kDw3XB) * S), dim3(kDw3Threads), lds, s, child, g, parent, maxes, M, X, KC, S, part))
+            return rc;
         const size_t n = (size_t)X * H * Y;
-        hipLaunchKernelGGL(tri_dw2_reduce_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, part, S, n, d_w);
+        if (int rc = launch("tri_dw2_reduce_kernel", tri_dw2_reduce_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, part, S, n, d_w)) return rc;
     }
-    return check_launch("trilinear_backward (fp16 parts)");
+    return 0;
 }
 
 template <bool F32IN>
@@ -1159,22 +1146,25 @@ static int run_tri_backward(const void* child, const void* w, const void* parent
     const void* g_op = g;   // the cotangent in the operand type, row-major
     if constexpr (!F32IN) {
         if (g_is_bf16) gB = (T*)const_cast<void*>(g);   // already in the operand type: no copy
-        else hipLaunchKernelGGL(tri_cast_bf16_kernel, dim3(512), dim3(256), 0, s, (const float*)g, (uint16_t*)gB, (size_t)M * H);
+        else if (int rc = launch("tri_cast_bf16_kernel", tri_cast_bf16_kernel, dim3(512), dim3(256), 0, s, (const float*)g, (uint16_t*)gB, (size_t)M * H))
+            return rc;
         g_op = gB;
     }
     bool permuted = false;
     if (d_child && d_parent && H <= 128 && X % 16 == 0 && X <= 16 * kTriWaves * kTriHPW && Y % 16 == 0 && Y <= 16 * kTriWaves * kTriHPW) {
-        hipLaunchKernelGGL((tri_permute2_kernel<T>), dim3(X, (Y + 31) / 32), dim3(256), 0, s, (const T*)w, wA, wB, X, H, Y);
+        if (int rc = launch("tri_permute2_kernel", tri_permute2_kernel<T>, dim3(X, (Y + 31) / 32), dim3(256), 0, s, (const T*)w, wA, wB, X, H, Y)) return rc;
         permuted = true;
     }
     if (d_child) {   // d_child[m,x] = sum_y p[m,y] * sum_h wA[y,x,h] g[m,h]: roles (c, w, p) := (p, wA, g); "X" = Y, "H" = X, "Y" = H
         if (X % 16 || X > 16 * kTriWaves * kTriHPW) return set_error(VLG_ERR_SHAPE, "trilinear_backward: X=%d must be a multiple of 16 and <= 128", X);
-        if (!permuted) hipLaunchKernelGGL((tri_permute_kernel<T>), dim3(pblocks), dim3(256), 0, s, (const T*)w, wA, X, H, Y, 0);
+        if (!permuted)
+            if (int rc = launch("tri_permute_kernel", tri_permute_kernel<T>, dim3(pblocks), dim3(256), 0, s, (const T*)w, wA, X, H, Y, 0)) return rc;
         if (int rc = dispatch_tri(parent, wA, g_op, M, Y, X, H, F32IN, d_child, s, F32IN ? nullptr : reinterpret_cast<float*>(ws + p.off_part))) return rc;
     }
     if (d_parent) {  // d_parent[m,y] = sum_x c[m,x] * sum_h wB[x,y,h] g[m,h]: roles (c, w, p) := (c, wB, g); "H" = Y, "Y" = H
         if (Y % 16 || Y > 16 * kTriWaves * kTriHPW) return set_error(VLG_ERR_SHAPE, "trilinear_backward: Y=%d must be a multiple of 16 and <= 128", Y);
-        if (!permuted) hipLaunchKernelGGL((tri_permute_kernel<T>), dim3(pblocks), dim3(256), 0, s, (const T*)w, wB, X, H, Y, 1);
+        if (!permuted)
+            if (int rc = launch("tri_permute_kernel", tri_permute_kernel<T>, dim3(pblocks), dim3(256), 0, s, (const T*)w, wB, X, H, Y, 1)) return rc;
         if (int rc = dispatch_tri(child, wB, g_op, M, X, Y, H, F32IN, d_parent, s, F32IN ? nullptr : reinterpret_cast<float*>(ws + p.off_part))) return rc;
     }
     if (d_w && dw2_applies(M, X, H, Y, F32IN)) {
@@ -1184,30 +1174,27 @@ static int run_tri_backward(const void* child, const void* w, const void* parent
             const int Sx = S;   // a trailing chunk may be empty (its partial tile is then zero)
             float* part = reinterpret_cast<float*>(ws + p.off_part);
             const size_t lds = 2 * (size_t)(kDw2XB + 1) * kDw2Stage * kDw2Pitch;   // 110 KB
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(tri_dw2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return set_error((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-            hipLaunchKernelGGL(tri_dw2_kernel, dim3((X / kDw2XB) * Sx), dim3(kDw2Threads), lds, s, (const uint16_t*)child, (const uint16_t*)gB,
-                               (const uint16_t*)parent, M, X, KC, Sx, part);
+            if (int rc = launch("tri_dw2_kernel", tri_dw2_kernel, dim3((X / kDw2XB) * Sx), dim3(kDw2Threads), lds, s, (const uint16_t*)child,
+                                (const uint16_t*)gB, (const uint16_t*)parent, M, X, KC, Sx, part))
+                return rc;
             const size_t n = (size_t)X * H * Y;
-            hipLaunchKernelGGL(tri_dw2_reduce_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, part, Sx, n, d_w);
+            if (int rc = launch("tri_dw2_reduce_kernel", tri_dw2_reduce_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, part, Sx, n, d_w))
+                return rc;
         }
     } else if (d_w) {
         if (Y > 16 * kDwYT || Y % 16) return set_error(VLG_ERR_SHAPE, "trilinear_backward: Y=%d must be a multiple of 16 and <= 128", Y);
         const int Mp = (int)p.Mp;
         dim3 tb(256);
-        hipLaunchKernelGGL((tri_transpose_kernel<T, false>), dim3((Mp + 31) / 32, (X + 31) / 32), tb, 0, s, child, cT, M, X, Mp);
-        if (!F32IN && g_is_bf16)
-            hipLaunchKernelGGL((tri_transpose_kernel<T, false>), dim3((Mp + 31) / 32, (H + 31) / 32), tb, 0, s, g, gT, M, H, Mp);
-        else
-            hipLaunchKernelGGL((tri_transpose_kernel<T, true>), dim3((Mp + 31) / 32, (H + 31) / 32), tb, 0, s, g, gT, M, H, Mp);
-        hipLaunchKernelGGL((tri_transpose_kernel<T, false>), dim3((Mp + 31) / 32, (Y + 31) / 32), tb, 0, s, parent, pT, M, Y, Mp);
+        if (int rc = launch("tri_transpose_kernel", tri_transpose_kernel<T, false>, dim3((Mp + 31) / 32, (X + 31) / 32), tb, 0, s, child, cT, M, X, Mp))
+            return rc;
+        auto kg = !F32IN && g_is_bf16 ? tri_transpose_kernel<T, false> : tri_transpose_kernel<T, true>;
+        if (int rc = launch("tri_transpose_kernel", kg, dim3((Mp + 31) / 32, (H + 31) / 32), tb, 0, s, g, gT, M, H, Mp)) return rc;
+        if (int rc = launch("tri_transpose_kernel", tri_transpose_kernel<T, false>, dim3((Mp + 31) / 32, (Y + 31) / 32), tb, 0, s, parent, pT, M, Y, Mp))
+            return rc;
         const size_t lds = sizeof(float) * 4 * (size_t)(kDwSplit - 1) * kDwHT * kDwYT * 64;   // 96 KB
-        auto k = tri_dw_kernel<F32IN>;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return set_error((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        hipLaunchKernelGGL(k, dim3(X, ((H >> 4) + kDwHT - 1) / kDwHT), dim3(64 * kDwSplit), lds, s, cT, gT, pT, Mp, X, H, Y, d_w);
+        return launch("tri_dw_kernel", tri_dw_kernel<F32IN>, dim3(X, ((H >> 4) + kDwHT - 1) / kDwHT), dim3(64 * kDwSplit), lds, s, cT, gT, pT, Mp, X, H, Y, d_w);
     }
-    return check_launch("trilinear_backward");
+    return 0;
 }
 
 static int check_dims(const char* what, int M, int X, int H, int Y) {

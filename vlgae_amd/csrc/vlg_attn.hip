@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "vlg_common.h"
+#include "vlg_launch.h"
 #include "vlg_dp_core.h"   // F32In / BF16In element loaders
 #include "vlg_mfma.h"      // bf16x8 fragments
 
@@ -642,12 +643,20 @@ __global__ __launch_bounds__(64) void attn_fuse_mfma_kernel(
     attn_residual_layernorm_store(Y, erows, tile, gamma, beta, b, q0, Lq, h, eps, out);
 }
 
-template <typename In, int T>
-static void launch_attn_mfma(const void* vis, const void* txt, const void* vis_mid, const void* enc_x, const float* gamma,
-                             const float* beta, int B, int L, int V, int d, int h, float eps, float* out, hipStream_t s) {
+template <typename In>
+static int launch_attn_mfma(const void* vis, const void* txt, const void* vis_mid, const void* enc_x, const float* gamma,
+                            const float* beta, int B, int L, int V, int d, int h, float eps, float* out, hipStream_t s) {
     using P = const typename In::T*;
-    hipLaunchKernelGGL((attn_fuse_mfma_kernel<In, T>), dim3((L + 15) / 16, B), dim3(64), kStageBytes + sizeof(float) * 16 * (h + 4), s, (P)vis, (P)txt, (P)vis_mid,
-                       (P)enc_x, gamma, beta, L, V, d, h, eps, out);
+    auto go = [&](auto k) {
+        return launch("attn_fuse_mfma_kernel", k, dim3((L + 15) / 16, B), dim3(64), kStageBytes + sizeof(float) * 16 * (h + 4), s, (P)vis, (P)txt, (P)vis_mid,
+                      (P)enc_x, gamma, beta, L, V, d, h, eps, out);
+    };
+    switch (V > 48 ? 4 : (V + 15) / 16) {   // region tiles per chunk; V > 64 streams chunks of 64
+        case 1: return go(attn_fuse_mfma_kernel<In, 1>);
+        case 2: return go(attn_fuse_mfma_kernel<In, 2>);
+        case 3: return go(attn_fuse_mfma_kernel<In, 3>);
+        default: return go(attn_fuse_mfma_kernel<In, 4>);
+    }
 }
 
 // ---- many keys: the key-split form --------------------------------------------------------------------------
@@ -1585,6 +1594,21 @@ struct AttnBwdPlan {   // scratch carving shared by the size query and the launc
     }
 };
 
+// many keys: the chunk records, their merge per word tile, then the combine
+template <typename In>
+static int launch_attn_split(const AttnSplit& sp, const void* vis, const void* txt, const void* vis_mid, const void* enc_x, const float* gamma,
+                             const float* beta, int B, int L, int V, int d, int h, float eps, float* rec, float* merged, float* out, hipStream_t s) {
+    using P = const typename In::T*;
+    if (int rc = launch("attn_fuse_split_kernel", attn_fuse_split_kernel<In>, dim3((B * sp.NC + 7) / 8 * 8, sp.WT), dim3(64), kStageBytes, s, (P)vis, (P)txt,
+                        (P)vis_mid, L, V, d, h, sp.CK, sp.NC, B * sp.NC, rec))
+        return rc;
+    if (int rc = launch("attn_merge_records_kernel", attn_merge_records_kernel, dim3(sp.WT, B, ((h >> 4) + 3) / 4), dim3(64), 0, s, (const float*)rec, sp.NC, h,
+                        merged))
+        return rc;
+    return launch("attn_fuse_combine_kernel", attn_fuse_combine_kernel<In>, dim3(sp.WT, B), dim3(64), sizeof(float) * 16 * (h + 4), s, (const float*)merged, 1,
+                  (P)enc_x, gamma, beta, L, h, eps, out);
+}
+
 }  // namespace vlg
 
 extern "C" {
@@ -1619,31 +1643,11 @@ int vlg_attn_fuse(const void* vis, const void* txt, const void* vis_mid, const v
             const size_t need = sizeof(float) * (sp.records(B) + (size_t)B * sp.WT) * AttnSplit::record_floats(h);
             float* merged = saved ? saved : (float*)ws + sp.records(B) * AttnSplit::record_floats(h);
             if (!ws || ws_bytes < need) return set_error(VLG_ERR_WORKSPACE, "attn_fuse: workspace %zu bytes < %zu", ws_bytes, need);
-#define VLG_ATTN_SPLIT(INV)                                                                                                      \
-    do {                                                                                                                         \
-        hipLaunchKernelGGL((attn_fuse_split_kernel<INV>), dim3((B * sp.NC + 7) / 8 * 8, sp.WT), dim3(64), kStageBytes, s,         \
-                           (const INV::T*)vis, (const INV::T*)txt, (const INV::T*)vis_mid, L, V, d, h, sp.CK, sp.NC, B * sp.NC,  \
-                           (float*)ws);                                                                                          \
-        hipLaunchKernelGGL(attn_merge_records_kernel, dim3(sp.WT, B, ((h >> 4) + 3) / 4), dim3(64), 0, s, (const float*)ws, sp.NC, h, \
-                           merged);                                                                                              \
-        hipLaunchKernelGGL((attn_fuse_combine_kernel<INV>), dim3(sp.WT, B), dim3(64), sizeof(float) * 16 * (h + 4), s,           \
-                           (const float*)merged, 1, (const INV::T*)enc_x, gamma, beta, L, h, eps, out);                          \
-    } while (0)
-            if (in_dtype == VLG_F32) VLG_ATTN_SPLIT(F32In);
-            else VLG_ATTN_SPLIT(BF16In);
-#undef VLG_ATTN_SPLIT
-            return check_launch("attn_fuse_split_kernel");
+            return in_dtype == VLG_F32 ? launch_attn_split<F32In>(sp, vis, txt, vis_mid, enc_x, gamma, beta, B, L, V, d, h, eps, (float*)ws, merged, out, s)
+                                       : launch_attn_split<BF16In>(sp, vis, txt, vis_mid, enc_x, gamma, beta, B, L, V, d, h, eps, (float*)ws, merged, out, s);
         }
-#define VLG_ATTN(INV)                                                                                              \
-    switch (V > 48 ? 4 : (V + 15) / 16) { /* region tiles per chunk; V > 64 streams chunks of 64 */                  \
-        case 1: launch_attn_mfma<INV, 1>(vis, txt, vis_mid, enc_x, gamma, beta, B, L, V, d, h, eps, out, s); break; \
-        case 2: launch_attn_mfma<INV, 2>(vis, txt, vis_mid, enc_x, gamma, beta, B, L, V, d, h, eps, out, s); break; \
-        case 3: launch_attn_mfma<INV, 3>(vis, txt, vis_mid, enc_x, gamma, beta, B, L, V, d, h, eps, out, s); break; \
-        default: launch_attn_mfma<INV, 4>(vis, txt, vis_mid, enc_x, gamma, beta, B, L, V, d, h, eps, out, s); break; \
-    }
-        if (in_dtype == VLG_F32) { VLG_ATTN(F32In) } else { VLG_ATTN(BF16In) }
-#undef VLG_ATTN
-        return check_launch("attn_fuse_mfma_kernel");
+        return in_dtype == VLG_F32 ? launch_attn_mfma<F32In>(vis, txt, vis_mid, enc_x, gamma, beta, B, L, V, d, h, eps, out, s)
+                                   : launch_attn_mfma<BF16In>(vis, txt, vis_mid, enc_x, gamma, beta, B, L, V, d, h, eps, out, s);
     }
     const size_t tile_f = (size_t)kFT * (size_t)((d + 1) > h ? (d + 1) : h);
     const size_t per_q = (size_t)(d + 1) + V + h + 2;
@@ -1651,22 +1655,11 @@ int vlg_attn_fuse(const void* vis, const void* txt, const void* vis_mid, const v
     while (QC > 1 && sizeof(float) * (tile_f + per_q * QC) > 150 * 1024) QC >>= 1;
     const size_t lds = sizeof(float) * (tile_f + per_q * QC);
     if (lds > 150 * 1024) return set_error(VLG_ERR_SHAPE, "attn_fuse: V=%d d=%d h=%d exceed the LDS budget", V, d, h);
-#define VLG_LAUNCH(INV)                                                                                            \
-    do {                                                                                                           \
-        auto k = attn_fuse_kernel<INV>;                                                                            \
-        if (lds > 60 * 1024) {                                                                                     \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),                                   \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);             \
-            if (e != hipSuccess) return set_error((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));        \
-        }                                                                                                          \
-        hipLaunchKernelGGL(k, dim3((L + QC - 1) / QC, B), dim3(kAlignThreads), lds, s, (const INV::T*)vis,          \
-                           (const INV::T*)txt, (const INV::T*)vis_mid, (const INV::T*)enc_x, gamma, beta, L, V, d, \
-                           h, eps, QC, out_att, out);                                                              \
-    } while (0)
-    if (in_dtype == VLG_F32) VLG_LAUNCH(F32In);
-    else VLG_LAUNCH(BF16In);
+#define VLG_LAUNCH(INV)                                                                                                                      \
+    launch("attn_fuse_kernel", attn_fuse_kernel<INV>, dim3((L + QC - 1) / QC, B), dim3(kAlignThreads), lds, s, (const INV::T*)vis, (const INV::T*)txt, \
+           (const INV::T*)vis_mid, (const INV::T*)enc_x, gamma, beta, L, V, d, h, eps, QC, out_att, out)
+    return in_dtype == VLG_F32 ? VLG_LAUNCH(F32In) : VLG_LAUNCH(BF16In);
 #undef VLG_LAUNCH
-    return check_launch("attn_fuse_kernel");
 }
 
 
@@ -1679,10 +1672,10 @@ size_t vlg_attn_fuse_backward_workspace(int B, int L, int V, int d, int h, int g
 namespace vlg {
 
 template <typename In, typename GOut, int FTM>
-static void attn_backward_launch(const void* vis, const void* txt, const void* vis_mid, const void* enc_x, const float* gamma,
-                                 const float* dout, size_t ld_b, size_t ld_l, int B, int L, int V, int d, int h, float eps,
-                                 const AttnBwdPlan& p, const float* saved, float* wsf, void* d_vis, void* d_txt, void* d_vis_mid,
-                                 void* d_enc_x, float* d_gamma, float* d_beta, hipStream_t s) {
+static int attn_backward_launch(const void* vis, const void* txt, const void* vis_mid, const void* enc_x, const float* gamma,
+                                const float* dout, size_t ld_b, size_t ld_l, int B, int L, int V, int d, int h, float eps,
+                                const AttnBwdPlan& p, const float* saved, float* wsf, void* d_vis, void* d_txt, void* d_vis_mid,
+                                void* d_enc_x, float* d_gamma, float* d_beta, hipStream_t s) {
     using P = const typename In::T*;
     using G = typename GOut::T*;
     float *PT = wsf, *DST = PT + p.pt_floats, *part = DST + p.pt_floats, *rec = part + p.part_floats, *stats = rec + p.rec_floats,
@@ -1697,37 +1690,47 @@ static void attn_backward_launch(const void* vis, const void* txt, const void* v
         const float* merged = saved;   // the forward's merged records, when the caller kept them (vlg_attn_fuse's `saved`)
         if (!merged) {
             float* mine = rec + p.rec_floats - (size_t)B * p.WT * AttnSplit::record_floats(h);
-            hipLaunchKernelGGL((attn_fuse_split_kernel<In>), chunks, dim3(64), kStageBytes, s, (P)vis, (P)txt, (P)vis_mid, L, V, d, h, p.sp.CK,
-                               p.sp.NC, pairs, rec);
-            hipLaunchKernelGGL(attn_merge_records_kernel, dim3(p.WT, B, ((h >> 4) + 3) / 4), dim3(64), 0, s, (const float*)rec, p.sp.NC, h, mine);
+            if (int rc = launch("attn_fuse_split_kernel", attn_fuse_split_kernel<In>, chunks, dim3(64), kStageBytes, s, (P)vis, (P)txt, (P)vis_mid, L, V, d, h,
+                                p.sp.CK, p.sp.NC, pairs, rec))
+                return rc;
+            if (int rc = launch("attn_merge_records_kernel", attn_merge_records_kernel, dim3(p.WT, B, ((h >> 4) + 3) / 4), dim3(64), 0, s, (const float*)rec,
+                                p.sp.NC, h, mine))
+                return rc;
             merged = mine;
         }
-        hipLaunchKernelGGL((attn_bwd_combine_kernel<In, GOut>), tiles, dim3(64), lds, s, merged, 1, (P)enc_x, gamma, dout,
-                           ld_b, ld_l, L, h, eps, stats, part, dy_rows, (G)d_enc_x, (P)txt, d, p.Lp, dyT, txtT);
-        hipLaunchKernelGGL((attn_bwd_sweep_kernel<In, FTM>), chunks, dim3(64), (kSweepBytes + 4096 > kStageBytes ? kSweepBytes + 4096 : kStageBytes), s, (P)vis, (P)txt, (P)vis_mid, (const float*)dy_rows,
-                           (const float*)stats, L, V, d, h, p.sp.CK, p.sp.NC, pairs, PT, DST, p.Vp, p.Lp, rec);
-        hipLaunchKernelGGL((attn_bwd_dtxt_kernel<GOut>), dim3(p.WT, B, d >> 4), dim3(64), 0, s, (const float*)rec, p.sp.NC, L, d, (G)d_txt);
+        if (int rc = launch("attn_bwd_combine_kernel", attn_bwd_combine_kernel<In, GOut>, tiles, dim3(64), lds, s, merged, 1, (P)enc_x, gamma, dout, ld_b, ld_l,
+                            L, h, eps, stats, part, dy_rows, (G)d_enc_x, (P)txt, d, p.Lp, dyT, txtT))
+            return rc;
+        if (int rc = launch("attn_bwd_sweep_kernel", attn_bwd_sweep_kernel<In, FTM>, chunks, dim3(64),
+                            (kSweepBytes + 4096 > kStageBytes ? kSweepBytes + 4096 : kStageBytes), s, (P)vis, (P)txt, (P)vis_mid, (const float*)dy_rows,
+                            (const float*)stats, L, V, d, h, p.sp.CK, p.sp.NC, pairs, PT, DST, p.Vp, p.Lp, rec))
+            return rc;
+        if (int rc = launch("attn_bwd_dtxt_kernel", attn_bwd_dtxt_kernel<GOut>, dim3(p.WT, B, d >> 4), dim3(64), 0, s, (const float*)rec, p.sp.NC, L, d,
+                            (G)d_txt))
+            return rc;
     } else {
-#define VLG_WORDS(TT)                                                                                                              \
-    hipLaunchKernelGGL((attn_fuse_bwd_words_kernel<In, GOut, TT, FTM>), dim3(p.WT, B), dim3(64), lds_words, s, (P)vis, (P)txt, (P)vis_mid, \
-                       (P)enc_x, gamma, dout, ld_b, ld_l, L, V, d, h, eps, PT, DST, p.Vp, p.Lp, part, (G)d_txt, dy_rows, (G)d_enc_x, dyT, txtT)
-        switch (p.T) {
-            case 1: VLG_WORDS(1); break;
-            case 2: VLG_WORDS(2); break;
-            case 3: VLG_WORDS(3); break;
-            default: VLG_WORDS(4); break;
-        }
-#undef VLG_WORDS
+        auto words = [&](auto k) {
+            return launch("attn_fuse_bwd_words_kernel", k, dim3(p.WT, B), dim3(64), lds_words, s, (P)vis, (P)txt, (P)vis_mid, (P)enc_x, gamma, dout, ld_b, ld_l, L, V,
+                          d, h, eps, PT, DST, p.Vp, p.Lp, part, (G)d_txt, dy_rows, (G)d_enc_x, dyT, txtT);
+        };
+        if (int rc = p.T == 1   ? words(attn_fuse_bwd_words_kernel<In, GOut, 1, FTM>)
+                     : p.T == 2 ? words(attn_fuse_bwd_words_kernel<In, GOut, 2, FTM>)
+                     : p.T == 3 ? words(attn_fuse_bwd_words_kernel<In, GOut, 3, FTM>)
+                                : words(attn_fuse_bwd_words_kernel<In, GOut, 4, FTM>))
+            return rc;
     }
-    if constexpr (kIsBF16<In>)
-        hipLaunchKernelGGL((attn_bwd_regions_bf16_kernel<GOut, FTM>), dim3((V + 15) / 16, B), dim3(64),
-                           16 * ((h > d ? h : d) + 8) * sizeof(typename GOut::T), s, (const uint16_t*)txtT,
-                           (const uint16_t*)dyT, (const float*)PT, (const float*)DST, p.Vp, p.Lp, V, d, h, (G)d_vis_mid, (G)d_vis);
-    else
-        hipLaunchKernelGGL((attn_fuse_bwd_regions_kernel<In, GOut, FTM>), dim3((V + 15) / 16, B), dim3(64), 0, s, (P)txt,
-                           (const float*)dy_rows, (const float*)PT, (const float*)DST, p.Vp, p.Lp, L, V, d, h, (G)d_vis_mid, (G)d_vis);
-    hipLaunchKernelGGL(attn_fuse_bwd_affine_kernel, dim3((2 * h + 63) / 64), dim3(1024), 0, s, (const float*)part, B * p.WT, h, d_gamma,
-                       d_beta);
+    if constexpr (kIsBF16<In>) {
+        if (int rc = launch("attn_bwd_regions_bf16_kernel", attn_bwd_regions_bf16_kernel<GOut, FTM>, dim3((V + 15) / 16, B), dim3(64),
+                            16 * ((h > d ? h : d) + 8) * sizeof(typename GOut::T), s, (const uint16_t*)txtT, (const uint16_t*)dyT, (const float*)PT,
+                            (const float*)DST, p.Vp, p.Lp, V, d, h, (G)d_vis_mid, (G)d_vis))
+            return rc;
+    } else {
+        if (int rc = launch("attn_fuse_bwd_regions_kernel", attn_fuse_bwd_regions_kernel<In, GOut, FTM>, dim3((V + 15) / 16, B), dim3(64), 0, s, (P)txt,
+                            (const float*)dy_rows, (const float*)PT, (const float*)DST, p.Vp, p.Lp, L, V, d, h, (G)d_vis_mid, (G)d_vis))
+            return rc;
+    }
+    return launch("attn_fuse_bwd_affine_kernel", attn_fuse_bwd_affine_kernel, dim3((2 * h + 63) / 64), dim3(1024), 0, s, (const float*)part, B * p.WT, h,
+                  d_gamma, d_beta);
 }
 
 }  // namespace vlg
@@ -1764,19 +1767,12 @@ int vlg_attn_fuse_backward(const void* vis, const void* txt, const void* vis_mid
     if (!ws || ws_bytes < p.bytes)
         return set_error(VLG_ERR_WORKSPACE, "attn_fuse_backward: workspace %zu bytes < %zu", ws_bytes, p.bytes);
     float* wsf = (float*)ws;
-#define VLG_BW(INV, GO)                                                                                                          \
-    do {                                                                                                                         \
-        if (d > 128)                                                                                                             \
-            attn_backward_launch<INV, GO, 16>(vis, txt, vis_mid, enc_x, gamma, dout, (size_t)ld_dout_b, (size_t)ld_dout_l, B, L, V, d, h, \
-                                              eps, p, saved, wsf, d_vis, d_txt, d_vis_mid, d_enc_x, d_gamma, d_beta, s);         \
-        else                                                                                                                     \
-            attn_backward_launch<INV, GO, 8>(vis, txt, vis_mid, enc_x, gamma, dout, (size_t)ld_dout_b, (size_t)ld_dout_l, B, L, V, d, h,  \
-                                             eps, p, saved, wsf, d_vis, d_txt, d_vis_mid, d_enc_x, d_gamma, d_beta, s);          \
-    } while (0)
-    if (in_dtype == VLG_F32) VLG_BW(F32In, F32Grad);
-    else if (grad_dtype == VLG_F32) VLG_BW(BF16In, F32Grad);
-    else VLG_BW(BF16In, BF16Grad);
+#define VLG_BW(INV, GO, FTM)                                                                                                                 \
+    attn_backward_launch<INV, GO, FTM>(vis, txt, vis_mid, enc_x, gamma, dout, (size_t)ld_dout_b, (size_t)ld_dout_l, B, L, V, d, h, eps, p, saved, wsf, \
+                                       d_vis, d_txt, d_vis_mid, d_enc_x, d_gamma, d_beta, s)
+    if (in_dtype == VLG_F32) return d > 128 ? VLG_BW(F32In, F32Grad, 16) : VLG_BW(F32In, F32Grad, 8);
+    if (grad_dtype == VLG_F32) return d > 128 ? VLG_BW(BF16In, F32Grad, 16) : VLG_BW(BF16In, F32Grad, 8);
+    return d > 128 ? VLG_BW(BF16In, BF16Grad, 16) : VLG_BW(BF16In, BF16Grad, 8);
 #undef VLG_BW
-    return check_launch("attn_fuse_backward");
 }
 }  // extern "C"

@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "vlg_common.h"
+#include "vlg_launch.h"
 
 namespace vlg {
 
@@ -116,7 +117,6 @@ int vlg_step_batch_prepare(const int64_t* lengths, const int64_t* tag, const uin
                       {0, add_rel ? 1 : -1, add_attr ? 1 + (add_rel != 0) : -1}};
     // the two coefficients as torch.tensor([alpha, -(1.0 - alpha)], dtype=float32) rounds them: double arithmetic, one rounding
     const float c_mt = (float)alpha, c_max = (float)(-(1.0 - alpha)), eps = (float)1e-12;
-    hipLaunchKernelGGL(batch_prepare_kernel, dim3(B), dim3(kBatchThreads), 0, (hipStream_t)stream, lengths, tag, box_mask, B, L, R, Q, V,
-                       off_rel, off_attr, pos, S, prior_scale, c_mt, c_max, eps, vmask, pen, num_token, coef, seed_max);
-    return check_launch("batch_prepare_kernel");
+    return launch("batch_prepare_kernel", batch_prepare_kernel, dim3(B), dim3(kBatchThreads), 0, (hipStream_t)stream, lengths, tag, box_mask, B, L, R, Q, V,
+                  off_rel, off_attr, pos, S, prior_scale, c_mt, c_max, eps, vmask, pen, num_token, coef, seed_max);
 }

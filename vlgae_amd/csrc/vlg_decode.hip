@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "vlg_common.h"
+#include "vlg_launch.h"
 
 namespace vlg {
 
@@ -235,22 +236,10 @@ extern "C" int vlg_grounding_decode(float* logit, const float* pen, const uint8_
     if (G > row_groups) G = row_groups;
     if (G > 1 && (!ws || ws_bytes < vlg_grounding_decode_workspace(B, a.n_box))) G = 1;
     hipStream_t s = (hipStream_t)stream;
-    auto attr = [&](const void* k) -> int {
-        if (lds <= 64 * 1024) return 0;
-        hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        return e == hipSuccess ? 0 : set_error((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    };
-    if (G == 1) {
-        if (int rc = attr(reinterpret_cast<const void*>(grounding_decode_kernel<0>))) return rc;
-        hipLaunchKernelGGL(grounding_decode_kernel<0>, dim3(B), dim3(64 * kDecWaves), lds, s, a);
-    } else {
-        a.sel = static_cast<uint8_t*>(ws);
-        hipError_t e = hipMemsetAsync(ws, 0, (size_t)B * 2 * (size_t)(a.n_box > 0 ? a.n_box : 1), s);
-        if (e != hipSuccess) return set_error((int)e, "hipMemsetAsync: %s", hipGetErrorString(e));
-        if (int rc = attr(reinterpret_cast<const void*>(grounding_decode_kernel<1>))) return rc;
-        if (int rc = attr(reinterpret_cast<const void*>(grounding_decode_kernel<2>))) return rc;
-        hipLaunchKernelGGL(grounding_decode_kernel<1>, dim3(B, G), dim3(64 * kDecWaves), lds, s, a);
-        hipLaunchKernelGGL(grounding_decode_kernel<2>, dim3(B, G), dim3(64 * kDecWaves), lds, s, a);
-    }
-    return check_launch("grounding_decode_kernel");
+    if (G == 1) return launch("grounding_decode_kernel", grounding_decode_kernel<0>, dim3(B), dim3(64 * kDecWaves), lds, s, a);
+    a.sel = static_cast<uint8_t*>(ws);
+    hipError_t e = hipMemsetAsync(ws, 0, (size_t)B * 2 * (size_t)(a.n_box > 0 ? a.n_box : 1), s);
+    if (e != hipSuccess) return set_error((int)e, "hipMemsetAsync: %s", hipGetErrorString(e));
+    if (int rc = launch("grounding_decode_kernel", grounding_decode_kernel<1>, dim3(B, G), dim3(64 * kDecWaves), lds, s, a)) return rc;
+    return launch("grounding_decode_kernel", grounding_decode_kernel<2>, dim3(B, G), dim3(64 * kDecWaves), lds, s, a);
 }

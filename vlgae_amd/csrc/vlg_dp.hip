@@ -321,8 +321,7 @@ int vlg_selftest_xlane(int* scratch, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = hipMemsetAsync(scratch, 0, sizeof(int), s);
     if (e != hipSuccess) return vlg::set_error((int)e, "hipMemsetAsync: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(vlg::xlane_selftest_kernel, dim3(1), dim3(128), 0, s, scratch);
-    return vlg::check_launch("xlane_selftest_kernel");
+    return vlg::launch("xlane_selftest_kernel", vlg::xlane_selftest_kernel, dim3(1), dim3(128), 0, s, scratch);
 }
 
 int vlg_dmv1o_merge(const void* dec, const void* attach, const void* root, int B, int L, int in_dtype, float one,
@@ -335,23 +334,21 @@ int vlg_dmv1o_merge(const void* dec, const void* attach, const void* root, int B
     const int blocks = (int)((total + threads - 1) / threads < 4096 ? (total + threads - 1) / threads : 4096);
     hipStream_t s = (hipStream_t)stream;
     if (in_dtype == VLG_F32)
-        hipLaunchKernelGGL(vlg::merge_kernel<vlg::F32In>, dim3(blocks), dim3(threads), 0, s, (const float*)dec,
-                           (const float*)attach, (const float*)root, B, L, one, zero, dec_wroot, attach_wroot);
+        return vlg::launch("merge_kernel", vlg::merge_kernel<vlg::F32In>, dim3(blocks), dim3(threads), 0, s, (const float*)dec, (const float*)attach,
+                           (const float*)root, B, L, one, zero, dec_wroot, attach_wroot);
     else if (in_dtype == VLG_BF16)
-        hipLaunchKernelGGL(vlg::merge_kernel<vlg::BF16In>, dim3(blocks), dim3(threads), 0, s, (const uint16_t*)dec,
-                           (const uint16_t*)attach, (const uint16_t*)root, B, L, one, zero, dec_wroot, attach_wroot);
+        return vlg::launch("merge_kernel", vlg::merge_kernel<vlg::BF16In>, dim3(blocks), dim3(threads), 0, s, (const uint16_t*)dec, (const uint16_t*)attach,
+                           (const uint16_t*)root, B, L, one, zero, dec_wroot, attach_wroot);
     else
         return vlg::set_error(VLG_ERR_DTYPE, "merge: in_dtype %d", in_dtype);
-    return vlg::check_launch("merge_kernel");
 }
 
 int vlg_dmv1o_count_sum(const float* grad_dec, const float* grad_attach, int B, int N, float* out, void* stream) {
     if (B < 0 || N < 2) return vlg::set_error(VLG_ERR_SHAPE, "count_sum: need B >= 0 and N >= 2 (got B=%d N=%d)", B, N);
     if (!grad_dec || !grad_attach || !out) return vlg::set_error(VLG_ERR_ARG, "count_sum: null buffer");
     const int Md = N * 8, Ma = N * N * 2;
-    hipLaunchKernelGGL(vlg::count_sum_kernel, dim3((Md + Ma + 63) / 64), dim3(1024), 0, (hipStream_t)stream, grad_dec,
-                       grad_attach, B, Md, Ma, out);
-    return vlg::check_launch("count_sum_kernel");
+    return vlg::launch("count_sum_kernel", vlg::count_sum_kernel, dim3((Md + Ma + 63) / 64), dim3(1024), 0, (hipStream_t)stream, grad_dec, grad_attach, B, Md,
+                       Ma, out);
 }
 
 int vlg_scale_counts(const float* counts_a, const float* counts_b, const float* g, int g_stride, int B, int n_a, int n_b,
@@ -363,12 +360,11 @@ int vlg_scale_counts(const float* counts_a, const float* counts_b, const float* 
     if (B == 0 || n_a + n_b == 0) return 0;
     const dim3 grid((n_a + n_b + 255) / 256, B);
     if (out_dtype == VLG_F32)
-        hipLaunchKernelGGL(vlg::scale_counts_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, counts_a, counts_b, g, g_stride, n_a,
-                           n_b, (float*)out_a, (float*)out_b);
+        return vlg::launch("scale_counts_kernel", vlg::scale_counts_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, counts_a, counts_b, g, g_stride,
+                           n_a, n_b, (float*)out_a, (float*)out_b);
     else
-        hipLaunchKernelGGL(vlg::scale_counts_kernel<__bf16>, grid, dim3(256), 0, (hipStream_t)stream, counts_a, counts_b, g,
-                           g_stride, n_a, n_b, (__bf16*)out_a, (__bf16*)out_b);
-    return vlg::check_launch("scale_counts_kernel");
+        return vlg::launch("scale_counts_kernel", vlg::scale_counts_kernel<__bf16>, grid, dim3(256), 0, (hipStream_t)stream, counts_a, counts_b, g, g_stride,
+                           n_a, n_b, (__bf16*)out_a, (__bf16*)out_b);
 }
 
 }  // extern "C"

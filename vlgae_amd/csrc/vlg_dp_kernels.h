@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "vlg_common.h"
+#include "vlg_launch.h"
 #include "vlg_dp_core.h"
 
 namespace vlg {
@@ -481,45 +482,26 @@ VLG_DP_DECLARE(2, DepArgs)
 #undef VLG_DP_DECLARE
 int VLG_DP_INST_NAME(2, 1, 2)(bool bwd, int mode, const DepArgs& a);   // DepTree / Max on ValSumIn: arc = [B,N,N,2] fp32 marginals
 
-template <typename K>
-static int prep(K kernel, size_t lds) {
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return set_error((int)e, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu): %s", lds,
-                                              hipGetErrorString(e));
-    }
-    return 0;
-}
-
 template <int SR, int MODE, bool BWD, typename In>
 static int launch_dmv(const DmvArgs& a) {
-    auto k = dmv1o_kernel<SR, MODE, BWD, In>;
-    if (int rc = prep(k, a.lds)) return rc;
-    hipLaunchKernelGGL(k, dim3(a.B), dim3(kThreads), a.lds, a.s, (const typename In::T*)a.dec,
-                       (const typename In::T*)a.attach, a.lengths, a.N, a.glogZ, a.logZ, a.gdec, a.gatt,
-                       (long long*)a.heads, (char*)a.ws, a.ws_stride);
-    return check_launch("dmv1o_kernel");
+    return launch("dmv1o_kernel", dmv1o_kernel<SR, MODE, BWD, In>, dim3(a.B), dim3(kThreads), a.lds, a.s, (const typename In::T*)a.dec,
+                  (const typename In::T*)a.attach, a.lengths, a.N, a.glogZ, a.logZ, a.gdec, a.gatt, (long long*)a.heads,
+                  (char*)a.ws, a.ws_stride);
 }
 
 template <int SR, int MODE, bool BWD, typename In>
 static int launch_rules(const RulesArgs& a) {
-    auto k = dmv1o_rules_kernel<SR, MODE, BWD, In>;
-    if (int rc = prep(k, a.lds)) return rc;
-    hipLaunchKernelGGL(k, dim3(a.B), dim3(kThreads), a.lds, a.s, (const typename In::T*)a.rule,
-                       (const typename In::T*)a.dec, (const typename In::T*)a.root, a.root_stride, a.token, a.head_mask,
-                       a.lengths, a.L, a.T, a.fill, a.glogZ, a.logZ, a.g_rule, a.g_dec, a.g_root, (long long*)a.heads,
-                       (char*)a.ws, a.ws_stride);
-    return check_launch("dmv1o_rules_kernel");
+    return launch("dmv1o_rules_kernel", dmv1o_rules_kernel<SR, MODE, BWD, In>, dim3(a.B), dim3(kThreads), a.lds, a.s,
+                  (const typename In::T*)a.rule, (const typename In::T*)a.dec, (const typename In::T*)a.root, a.root_stride,
+                  a.token, a.head_mask, a.lengths, a.L, a.T, a.fill, a.glogZ, a.logZ, a.g_rule, a.g_dec, a.g_root,
+                  (long long*)a.heads, (char*)a.ws, a.ws_stride);
 }
 
 template <int SR, int MODE, bool BWD, typename In>
 static int launch_dep(const DepArgs& a) {
-    auto k = deptree_kernel<SR, MODE, BWD, In>;
-    if (int rc = prep(k, a.lds)) return rc;
-    hipLaunchKernelGGL(k, dim3(a.B), dim3(kThreads), a.lds, a.s, (const typename In::T*)a.arc, a.lengths, a.N, a.glogZ,
-                       a.logZ, a.garc, (long long*)a.heads, (char*)a.ws, a.ws_stride);
-    return check_launch("deptree_kernel");
+    return launch("deptree_kernel", deptree_kernel<SR, MODE, BWD, In>, dim3(a.B), dim3(kThreads), a.lds, a.s,
+                  (const typename In::T*)a.arc, a.lengths, a.N, a.glogZ, a.logZ, a.garc, (long long*)a.heads, (char*)a.ws,
+                  a.ws_stride);
 }
 
 }  // namespace vlg

@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "vlg_common.h"
+#include "vlg_launch.h"
 #include "vlg_rng.h"
 #include "vlg_rows.h"
 
@@ -272,13 +273,10 @@ int vlg_dropout(const void* x, const float* mask, int shared_rows, const uint64_
     const size_t n = (size_t)rows * (cols >> 3);
     const dim3 grid((unsigned)((n + kEncThreads - 1) / kEncThreads));
     hipStream_t s = (hipStream_t)stream;
-#define VLG_DROP(A, O) hipLaunchKernelGGL((dropout_kernel<A, O>), grid, dim3(kEncThreads), 0, s, (const A*)x, mask, shared_rows, rng, site, thr, scale, (const O*)add, (O*)out, (size_t)rows, cols)
-    if (dtype == VLG_F32 && out_dtype == VLG_F32) VLG_DROP(float, float);
-    else if (dtype == VLG_F32) VLG_DROP(float, uint16_t);
-    else if (out_dtype == VLG_F32) VLG_DROP(uint16_t, float);
-    else VLG_DROP(uint16_t, uint16_t);
+#define VLG_DROP(A, O) launch("dropout_kernel", dropout_kernel<A, O>, grid, dim3(kEncThreads), 0, s, (const A*)x, mask, shared_rows, rng, site, thr, scale, (const O*)add, (O*)out, (size_t)rows, cols)
+    if (dtype == VLG_F32) return out_dtype == VLG_F32 ? VLG_DROP(float, float) : VLG_DROP(float, uint16_t);
+    return out_dtype == VLG_F32 ? VLG_DROP(uint16_t, float) : VLG_DROP(uint16_t, uint16_t);
 #undef VLG_DROP
-    return check_launch("dropout_kernel");
 }
 
 int vlg_dropout_mask(const uint64_t* rng, unsigned site, float p, float* out, long long n, void* stream) {
@@ -287,15 +285,13 @@ int vlg_dropout_mask(const uint64_t* rng, unsigned site, float p, float* out, lo
     if (n == 0) return 0;
     if (!rng || !out) return set_error(VLG_ERR_ARG, "dropout_mask: null buffer");
     const size_t groups = ((size_t)n + 7) / 8;
-    hipLaunchKernelGGL(dropout_mask_kernel, dim3((unsigned)((groups + kEncThreads - 1) / kEncThreads)), dim3(kEncThreads), 0, (hipStream_t)stream, rng, site,
-                       drop_threshold(p), drop_scale(p), out, (size_t)n);
-    return check_launch("dropout_mask_kernel");
+    return launch("dropout_mask_kernel", dropout_mask_kernel, dim3((unsigned)((groups + kEncThreads - 1) / kEncThreads)), dim3(kEncThreads), 0,
+                  (hipStream_t)stream, rng, site, drop_threshold(p), drop_scale(p), out, (size_t)n);
 }
 
 int vlg_rng_advance(uint64_t* rng, void* stream) {
     if (!rng) return vlg::set_error(VLG_ERR_ARG, "rng_advance: null state");
-    hipLaunchKernelGGL(vlg::rng_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, rng);
-    return vlg::check_launch("rng_advance_kernel");
+    return vlg::launch("rng_advance_kernel", vlg::rng_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, rng);
 }
 
 static int vis_check(const char* what, int B, int R, int H, int V, int ldp, int dtype, int col_box, int col_rel, int col_attr, int off_box, int off_rel,
@@ -323,9 +319,8 @@ int vlg_vis_encoder(const void* P, const void* C, int B, int R, int H, int V, in
     if (!P || !C || !mid) return set_error(VLG_ERR_ARG, "vis_encoder: null buffer");
     const VisArgs a{P, C, mid, R, H, V, ldp, col_box, col_rel, col_attr, off_box, off_rel, off_attr, off_img, slope};
     const dim3 grid((off_rel >= 0 ? R : 0) + 1 + (off_attr >= 0 ? 1 : 0), B);
-    if (dtype == VLG_F32) hipLaunchKernelGGL(vis_encoder_fwd_kernel<float>, grid, dim3(kEncThreads), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(vis_encoder_fwd_kernel<uint16_t>, grid, dim3(kEncThreads), 0, (hipStream_t)stream, a);
-    return check_launch("vis_encoder_fwd_kernel");
+    if (dtype == VLG_F32) return launch("vis_encoder_fwd_kernel", vis_encoder_fwd_kernel<float>, grid, dim3(kEncThreads), 0, (hipStream_t)stream, a);
+    else return launch("vis_encoder_fwd_kernel", vis_encoder_fwd_kernel<uint16_t>, grid, dim3(kEncThreads), 0, (hipStream_t)stream, a);
 }
 
 int vlg_vis_encoder_backward(const void* P, const void* C, const void* grad_mid, int B, int R, int H, int V, int ldp, int col_box, int col_rel, int col_attr,
@@ -337,9 +332,8 @@ int vlg_vis_encoder_backward(const void* P, const void* C, const void* grad_mid,
     const dim3 grid((off_rel >= 0 ? R : 0) + 1 + (off_attr >= 0 ? 1 : 0), B);
     hipStream_t s = (hipStream_t)stream;
     if (off_rel < 0) {    // one launch: the per-image sums come out of the workgroups that hold whole images
-        if (dtype == VLG_F32) hipLaunchKernelGGL(vis_encoder_bwd_kernel<float>, grid, dim3(kEncThreads), 0, s, a);
-        else hipLaunchKernelGGL(vis_encoder_bwd_kernel<uint16_t>, grid, dim3(kEncThreads), 0, s, a);
-        return check_launch("vis_encoder_bwd_kernel");
+        if (dtype == VLG_F32) return launch("vis_encoder_bwd_kernel", vis_encoder_bwd_kernel<float>, grid, dim3(kEncThreads), 0, s, a);
+        else return launch("vis_encoder_bwd_kernel", vis_encoder_bwd_kernel<uint16_t>, grid, dim3(kEncThreads), 0, s, a);
     }
     // the per-image sums run over the columns [0, cols): the encoders' blocks must be adjacent from column 0 in the order box | rel | attr
     // (what the Python mirror lays out; a C caller with another layout must hear about it -- ADVICE r05)
@@ -349,16 +343,17 @@ int vlg_vis_encoder_backward(const void* P, const void* C, const void* grad_mid,
     const int cols = H * (1 + (off_rel >= 0) + (off_attr >= 0));
     const size_t n = (size_t)B * (cols >> 2);
     if (dtype == VLG_F32) {
-        hipLaunchKernelGGL(vis_encoder_bwd_kernel<float>, grid, dim3(kEncThreads), 0, s, a);
-        if (int rc = check_launch("vis_encoder_bwd_kernel")) return rc;
-        hipLaunchKernelGGL(vis_segsum_kernel<float>, dim3((unsigned)((n + kEncThreads - 1) / kEncThreads)), dim3(kEncThreads), 0, s, (const float*)dP, (float*)dC, B, R, cols, ldp);
+        if (int rc = launch("vis_encoder_bwd_kernel", vis_encoder_bwd_kernel<float>, grid, dim3(kEncThreads), 0, s, a)) return rc;
+        if (int rc = launch("vis_segsum_kernel", vis_segsum_kernel<float>, dim3((unsigned)((n + kEncThreads - 1) / kEncThreads)), dim3(kEncThreads), 0, s,
+                            (const float*)dP, (float*)dC, B, R, cols, ldp))
+            return rc;
     } else {
-        hipLaunchKernelGGL(vis_encoder_bwd_kernel<uint16_t>, grid, dim3(kEncThreads), 0, s, a);
-        if (int rc = check_launch("vis_encoder_bwd_kernel")) return rc;
-        hipLaunchKernelGGL(vis_segsum_kernel<uint16_t>, dim3((unsigned)((n + kEncThreads - 1) / kEncThreads)), dim3(kEncThreads), 0, s, (const uint16_t*)dP, (uint16_t*)dC, B, R, cols,
-                           ldp);
+        if (int rc = launch("vis_encoder_bwd_kernel", vis_encoder_bwd_kernel<uint16_t>, grid, dim3(kEncThreads), 0, s, a)) return rc;
+        if (int rc = launch("vis_segsum_kernel", vis_segsum_kernel<uint16_t>, dim3((unsigned)((n + kEncThreads - 1) / kEncThreads)), dim3(kEncThreads), 0, s,
+                            (const uint16_t*)dP, (uint16_t*)dC, B, R, cols, ldp))
+            return rc;
     }
-    return check_launch("vis_segsum_kernel");
+    return 0;
 }
 
 }  // extern "C"

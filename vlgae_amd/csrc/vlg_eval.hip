@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "vlg_common.h"
+#include "vlg_launch.h"
 
 namespace vlg {
 
@@ -213,9 +214,7 @@ int vlg_eval_metrics(const int64_t* pred_arc, int ld_pred, const int64_t* gold_a
     const EvalArgs a{pred_arc, ld_pred, gold_arc, mask, lengths, factor2img, n_box_args ? top5 : nullptr, vis_box, sg_box, sg_type, sg_mask,
                      B, L, Q, R, V, off_rel, off_attr, static_cast<long long*>(ws)};
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(eval_sentence_kernel, dim3(B), dim3(kEvalThreads), 0, s, a);
-    if (int rc = check_launch("eval_sentence_kernel")) return rc;
-    hipLaunchKernelGGL(eval_reduce_kernel, dim3(1), dim3(kEvalThreads), 0, s, static_cast<const long long*>(ws), B, factor2img != nullptr,
-                       n_box_args != 0, loss, reinterpret_cast<long long*>(counters));
-    return check_launch("eval_reduce_kernel");
+    if (int rc = launch("eval_sentence_kernel", eval_sentence_kernel, dim3(B), dim3(kEvalThreads), 0, s, a)) return rc;
+    return launch("eval_reduce_kernel", eval_reduce_kernel, dim3(1), dim3(kEvalThreads), 0, s, static_cast<const long long*>(ws), B, factor2img != nullptr,
+                  n_box_args != 0, loss, reinterpret_cast<long long*>(counters));
 }

@@ -20,6 +20,7 @@
 #include <initializer_list>
 
 #include "vlg_common.h"
+#include "vlg_launch.h"
 #include "vlg_rng.h"
 #include "vlg_rows.h"
 
@@ -298,12 +299,11 @@ int vlg_ff_mlp_act(void* x, const void* cterm, const float* drop_head, const flo
     const dim3 grid = ff_grid((size_t)(M0 + Ms) * (H / 8));
     hipStream_t s = (hipStream_t)stream;
     if (act_dtype == VLG_BF16)
-        hipLaunchKernelGGL(ff_mlp_act_kernel<uint16_t>, grid, dim3(kFfThreads), 0, s, (uint16_t*)x, (const uint16_t*)cterm, drop_head, drop_small,
-                           (int)M0, Ms, L, H, slope);
+        return launch("ff_mlp_act_kernel", ff_mlp_act_kernel<uint16_t>, grid, dim3(kFfThreads), 0, s, (uint16_t*)x, (const uint16_t*)cterm, drop_head,
+                      drop_small, (int)M0, Ms, L, H, slope);
     else
-        hipLaunchKernelGGL(ff_mlp_act_kernel<float>, grid, dim3(kFfThreads), 0, s, (float*)x, (const float*)cterm, drop_head, drop_small, (int)M0,
-                           Ms, L, H, slope);
-    return check_launch("ff_mlp_act_kernel");
+        return launch("ff_mlp_act_kernel", ff_mlp_act_kernel<float>, grid, dim3(kFfThreads), 0, s, (float*)x, (const float*)cterm, drop_head, drop_small,
+                      (int)M0, Ms, L, H, slope);
 }
 
 int vlg_ff_act(const void* in, const void* residual, const void* mask, float mask_scale, const uint64_t* rng, unsigned site, float p, void* out,
@@ -321,12 +321,11 @@ int vlg_ff_act(const void* in, const void* residual, const void* mask, float mas
     const dim3 grid = ff_grid(rows * (H / 8));
     hipStream_t s = (hipStream_t)stream;
     if (act_dtype == VLG_BF16)
-        hipLaunchKernelGGL(ff_act_kernel<uint16_t>, grid, dim3(kFfThreads), 0, s, (const uint16_t*)in, (const uint16_t*)residual, (const uint16_t*)mask,
-                           mask_scale, rng, site, thr, (uint16_t*)out, rows, J, H, swap, slope);
+        return launch("ff_act_kernel", ff_act_kernel<uint16_t>, grid, dim3(kFfThreads), 0, s, (const uint16_t*)in, (const uint16_t*)residual,
+                      (const uint16_t*)mask, mask_scale, rng, site, thr, (uint16_t*)out, rows, J, H, swap, slope);
     else
-        hipLaunchKernelGGL(ff_act_kernel<float>, grid, dim3(kFfThreads), 0, s, (const float*)in, (const float*)residual, (const float*)mask, mask_scale,
-                           rng, site, thr, (float*)out, rows, J, H, swap, slope);
-    return check_launch("ff_act_kernel");
+        return launch("ff_act_kernel", ff_act_kernel<float>, grid, dim3(kFfThreads), 0, s, (const float*)in, (const float*)residual, (const float*)mask,
+                      mask_scale, rng, site, thr, (float*)out, rows, J, H, swap, slope);
 }
 
 int vlg_ff_act_backward(const void* g, const void* act, const void* mask, float mask_scale, const uint64_t* rng, unsigned site, float p, void* out,
@@ -343,12 +342,11 @@ int vlg_ff_act_backward(const void* g, const void* act, const void* mask, float 
     const dim3 grid = ff_grid((size_t)M * (H / 8));
     hipStream_t s = (hipStream_t)stream;
     if (act_dtype == VLG_BF16)
-        hipLaunchKernelGGL(ff_act_bwd_kernel<uint16_t>, grid, dim3(kFfThreads), 0, s, (const uint16_t*)g, (const uint16_t*)act, (const uint16_t*)mask,
-                           mask_scale, rng, site, thr, (uint16_t*)out, sum, (size_t)M, J, H, swap, accumulate, slope);
+        return launch("ff_act_bwd_kernel", ff_act_bwd_kernel<uint16_t>, grid, dim3(kFfThreads), 0, s, (const uint16_t*)g, (const uint16_t*)act,
+                      (const uint16_t*)mask, mask_scale, rng, site, thr, (uint16_t*)out, sum, (size_t)M, J, H, swap, accumulate, slope);
     else
-        hipLaunchKernelGGL(ff_act_bwd_kernel<float>, grid, dim3(kFfThreads), 0, s, (const float*)g, (const float*)act, (const float*)mask, mask_scale,
-                           rng, site, thr, (float*)out, sum, (size_t)M, J, H, swap, accumulate, slope);
-    return check_launch("ff_act_bwd_kernel");
+        return launch("ff_act_bwd_kernel", ff_act_bwd_kernel<float>, grid, dim3(kFfThreads), 0, s, (const float*)g, (const float*)act, (const float*)mask,
+                      mask_scale, rng, site, thr, (float*)out, sum, (size_t)M, J, H, swap, accumulate, slope);
 }
 
 int vlg_ff_mlp_act_backward(const float* gx, const void* t, const void* x, const float* drop_head, const float* drop_small, void* gpre, int B, int L,
@@ -363,12 +361,11 @@ int vlg_ff_mlp_act_backward(const float* gx, const void* t, const void* x, const
     const dim3 grid = ff_grid((size_t)(M0 + Ms) * (H / 8));
     hipStream_t s = (hipStream_t)stream;
     if (act_dtype == VLG_BF16)
-        hipLaunchKernelGGL(ff_mlp_act_bwd_kernel<uint16_t>, grid, dim3(kFfThreads), 0, s, gx, (const uint16_t*)t, (const uint16_t*)x, drop_head,
-                           drop_small, (uint16_t*)gpre, (int)M0, Ms, L, H, slope);
+        return launch("ff_mlp_act_bwd_kernel", ff_mlp_act_bwd_kernel<uint16_t>, grid, dim3(kFfThreads), 0, s, gx, (const uint16_t*)t, (const uint16_t*)x,
+                      drop_head, drop_small, (uint16_t*)gpre, (int)M0, Ms, L, H, slope);
     else
-        hipLaunchKernelGGL(ff_mlp_act_bwd_kernel<float>, grid, dim3(kFfThreads), 0, s, gx, (const float*)t, (const float*)x, drop_head, drop_small,
-                           (float*)gpre, (int)M0, Ms, L, H, slope);
-    return check_launch("ff_mlp_act_bwd_kernel");
+        return launch("ff_mlp_act_bwd_kernel", ff_mlp_act_bwd_kernel<float>, grid, dim3(kFfThreads), 0, s, gx, (const float*)t, (const float*)x, drop_head,
+                      drop_small, (float*)gpre, (int)M0, Ms, L, H, slope);
 }
 
 int vlg_ff_context_mean(const void* x, int in_dtype, int B, int L, int h, void* out, int out_dtype, void* stream) {
@@ -380,11 +377,14 @@ int vlg_ff_context_mean(const void* x, int in_dtype, int B, int L, int h, void* 
     if (!x || !out) return set_error(VLG_ERR_ARG, "ff_context_mean: null buffer");
     const dim3 grid(B, (h + 255) / 256);
     hipStream_t s = (hipStream_t)stream;
-    if (in_dtype == VLG_F32 && out_dtype == VLG_F32) hipLaunchKernelGGL((ff_colmean_kernel<float, float>), grid, dim3(256), 0, s, (const float*)x, L, h, (float*)out);
-    else if (in_dtype == VLG_F32) hipLaunchKernelGGL((ff_colmean_kernel<float, uint16_t>), grid, dim3(256), 0, s, (const float*)x, L, h, (uint16_t*)out);
-    else if (out_dtype == VLG_F32) hipLaunchKernelGGL((ff_colmean_kernel<uint16_t, float>), grid, dim3(256), 0, s, (const uint16_t*)x, L, h, (float*)out);
-    else hipLaunchKernelGGL((ff_colmean_kernel<uint16_t, uint16_t>), grid, dim3(256), 0, s, (const uint16_t*)x, L, h, (uint16_t*)out);
-    return check_launch("ff_colmean_kernel");
+    if (in_dtype == VLG_F32 && out_dtype == VLG_F32)
+        return launch("ff_colmean_kernel", ff_colmean_kernel<float, float>, grid, dim3(256), 0, s, (const float*)x, L, h, (float*)out);
+    else if (in_dtype == VLG_F32)
+        return launch("ff_colmean_kernel", ff_colmean_kernel<float, uint16_t>, grid, dim3(256), 0, s, (const float*)x, L, h, (uint16_t*)out);
+    else if (out_dtype == VLG_F32)
+        return launch("ff_colmean_kernel", ff_colmean_kernel<uint16_t, float>, grid, dim3(256), 0, s, (const uint16_t*)x, L, h, (float*)out);
+    else
+        return launch("ff_colmean_kernel", ff_colmean_kernel<uint16_t, uint16_t>, grid, dim3(256), 0, s, (const uint16_t*)x, L, h, (uint16_t*)out);
 }
 
 int vlg_ff_root_rule(const void* small, int ld, int T, int r, int act_dtype, float* root_rule, void* stream) {
@@ -394,9 +394,9 @@ int vlg_ff_root_rule(const void* small, int ld, int T, int r, int act_dtype, flo
     if (!small || !root_rule) return set_error(VLG_ERR_ARG, "ff_root_rule: null buffer");
     const size_t lds = sizeof(float) * ((size_t)T + 256);
     hipStream_t s = (hipStream_t)stream;
-    if (act_dtype == VLG_BF16) hipLaunchKernelGGL(ff_root_rule_kernel<uint16_t>, dim3(1), dim3(256), lds, s, (const uint16_t*)small, ld, T, r, 2 * r, r, root_rule);
-    else hipLaunchKernelGGL(ff_root_rule_kernel<float>, dim3(1), dim3(256), lds, s, (const float*)small, ld, T, r, 2 * r, r, root_rule);
-    return check_launch("ff_root_rule_kernel");
+    if (act_dtype == VLG_BF16)
+        return launch("ff_root_rule_kernel", ff_root_rule_kernel<uint16_t>, dim3(1), dim3(256), lds, s, (const uint16_t*)small, ld, T, r, 2 * r, r, root_rule);
+    else return launch("ff_root_rule_kernel", ff_root_rule_kernel<float>, dim3(1), dim3(256), lds, s, (const float*)small, ld, T, r, 2 * r, r, root_rule);
 }
 
 int vlg_ff_root_rule_backward(const void* small, int ld, int T, int r, int act_dtype, const float* root_rule, const float* g_root, const void* g_x2,
@@ -409,12 +409,11 @@ int vlg_ff_root_rule_backward(const void* small, int ld, int T, int r, int act_d
     const dim3 grid((4 * (T + 3) + 63) / 64);
     hipStream_t s = (hipStream_t)stream;
     if (act_dtype == VLG_BF16)
-        hipLaunchKernelGGL(ff_root_rule_bwd_kernel<uint16_t>, grid, dim3(256), sizeof(float) * (size_t)T, s, (const uint16_t*)small, ld, T, r, root_rule, g_root, (const uint16_t*)g_x2, ld_x2,
-                           (const uint16_t*)g_y2, ld_y2, (uint16_t*)g_small);
+        return launch("ff_root_rule_bwd_kernel", ff_root_rule_bwd_kernel<uint16_t>, grid, dim3(256), sizeof(float) * (size_t)T, s, (const uint16_t*)small, ld,
+                      T, r, root_rule, g_root, (const uint16_t*)g_x2, ld_x2, (const uint16_t*)g_y2, ld_y2, (uint16_t*)g_small);
     else
-        hipLaunchKernelGGL(ff_root_rule_bwd_kernel<float>, grid, dim3(256), sizeof(float) * (size_t)T, s, (const float*)small, ld, T, r, root_rule, g_root, (const float*)g_x2, ld_x2,
-                           (const float*)g_y2, ld_y2, (float*)g_small);
-    return check_launch("ff_root_rule_bwd_kernel");
+        return launch("ff_root_rule_bwd_kernel", ff_root_rule_bwd_kernel<float>, grid, dim3(256), sizeof(float) * (size_t)T, s, (const float*)small, ld, T, r,
+                      root_rule, g_root, (const float*)g_x2, ld_x2, (const float*)g_y2, ld_y2, (float*)g_small);
 }
 
 }  // extern "C"

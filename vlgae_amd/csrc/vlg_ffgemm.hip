@@ -23,6 +23,7 @@
 #include <algorithm>
 
 #include "vlg_common.h"
+#include "vlg_launch.h"
 #include "vlg_mfma.h"
 #include "vlg_rng.h"
 #include "vlg_rows.h"
@@ -470,48 +471,34 @@ int fg_mode(const FgArgs& a) {
 
 template <int KS, int M>
 int fg_launch_km(const FgArgs& a, int nb, hipStream_t s) {
-    static bool attr_set = false;
     constexpr int lds = fg_lds(KS * 32);
-    if (!attr_set && lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ff_gemm_act_kernel<KS, M>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return set_error((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
     const long long tiles = (a.rows + kFgRows - 1) / kFgRows;
     // ONE workgroup per CU holds its weight block for the whole launch (the block is re-read from the L2 by every workgroup: with 512
     // workgroups those reads -- 64 MB of 64-byte pieces out of the same 128 KB -- took ~15 us per launch); the tiles are dealt round-robin
     const int per_block = std::max(1, 256 / nb);
     const int gx = (int)std::min<long long>(tiles, per_block);
-    hipLaunchKernelGGL((ff_gemm_act_kernel<KS, M>), dim3(gx, nb), dim3(kFgThreads), lds, s, a);
-    return check_launch("ff_gemm_act_kernel");
+    return launch("ff_gemm_act_kernel", ff_gemm_act_kernel<KS, M>, dim3(gx, nb), dim3(kFgThreads), lds, s, a);
 }
 
 // the images with their options compiled in: the combinations vlgae_amd.parser_ff / align.linear_kn launch in a training step;
 // any other combination of a C-ABI caller takes the generic image (options read at run time)
 int fg_launch(const FgArgs& a, int k, int nb, hipStream_t s) {
     const int m = fg_mode(a);
-#define FG_CASE(KS_, M_) if (m == (M_)) return fg_launch_km<KS_, (M_)>(a, nb, s)
-    if (k == 32) {
-        FG_CASE(1, kMBwd);
-        return fg_launch_km<1, -1>(a, nb, s);
-    }
-    if (k == 512) {
-        FG_CASE(16, kMBwd);
-        FG_CASE(16, kMBwd | kMAdd);
-        return fg_launch_km<16, -1>(a, nb, s);
-    }
-    FG_CASE(8, 0);                                         // a plain layer
-    FG_CASE(8, kMRes);                                     // (no | has) bottlenecks + skip connection
-    FG_CASE(8, kMRes | kMRs1);                             // (left | right) bottlenecks + skip connection
-    FG_CASE(8, kMRng);                                     // direction stage + nn.Dropout
-    FG_CASE(8, kMBwd);
-    FG_CASE(8, kMBwd | kMRng);
-    FG_CASE(8, kMBwd | kMJ4 | kMSwap | kMSum);
-    FG_CASE(8, kMBwd | kMJ2 | kMSum | kMAcc);
-    FG_CASE(8, kMPlain);                                   // linear_kn
-    FG_CASE(8, kMPlain | kMRng);
+#define FG_CASE(KS_, M_) m == (M_) ? fg_launch_km<KS_, (M_)>(a, nb, s):
+    if (k == 32) return FG_CASE(1, kMBwd) fg_launch_km<1, -1>(a, nb, s);
+    if (k == 512) return FG_CASE(16, kMBwd) FG_CASE(16, kMBwd | kMAdd) fg_launch_km<16, -1>(a, nb, s);
+    return FG_CASE(8, 0)                                         // a plain layer
+           FG_CASE(8, kMRes)                                     // (no | has) bottlenecks + skip connection
+           FG_CASE(8, kMRes | kMRs1)                             // (left | right) bottlenecks + skip connection
+           FG_CASE(8, kMRng)                                     // direction stage + nn.Dropout
+           FG_CASE(8, kMBwd)
+           FG_CASE(8, kMBwd | kMRng)
+           FG_CASE(8, kMBwd | kMJ4 | kMSwap | kMSum)
+           FG_CASE(8, kMBwd | kMJ2 | kMSum | kMAcc)
+           FG_CASE(8, kMPlain)                                   // linear_kn
+           FG_CASE(8, kMPlain | kMRng)
+           fg_launch_km<8, -1>(a, nb, s);
 #undef FG_CASE
-    return fg_launch_km<8, -1>(a, nb, s);
 }
 
 int fg_check(const char* what, const void* x, int ldx, int k, const void* w, long long rows, const void* out) {
@@ -598,19 +585,18 @@ int vlg_ff_linear_act_chain2(const void* x, int ldx, long long rows, int backwar
     if (rows == 0) return 0;
     a.x = (const uint16_t*)x; a.ldx = ldx; a.rows = rows;
     b.x = (const uint16_t*)s1->out; b.ldx = kFgH; b.rows = rows;          // (the two-stage image reads it from LDS; the two-launch route from memory)
-    constexpr int lds = 3 * kFgRows * fg_pitch(256);        // 51 KB: below the 64 KB that need no attribute
-    static_assert(lds <= 64 * 1024, "dynamic LDS attribute needed");
+    constexpr int lds = 3 * kFgRows * fg_pitch(256);        // 51 KB
     const long long tiles = (rows + kFgRows - 1) / kFgRows;
     const dim3 grid((unsigned)std::min<long long>(tiles, 256));
     const int ma = fg_mode(a), mb = fg_mode(b);
-    if (ma == kMRng && mb == 0) hipLaunchKernelGGL((ff_gemm_act2_kernel<kMRng, 0>), grid, dim3(kFgThreads), lds, (hipStream_t)stream, a, b);
+    if (ma == kMRng && mb == 0) return launch("ff_gemm_act2_kernel", ff_gemm_act2_kernel<kMRng, 0>, grid, dim3(kFgThreads), lds, (hipStream_t)stream, a, b);
     else if (ma == (kMBwd | kMRng) && mb == (kMBwd | kMJ4 | kMSwap | kMSum))
-        hipLaunchKernelGGL((ff_gemm_act2_kernel<kMBwd | kMRng, kMBwd | kMJ4 | kMSwap | kMSum>), grid, dim3(kFgThreads), lds, (hipStream_t)stream, a, b);
+        return launch("ff_gemm_act2_kernel", ff_gemm_act2_kernel<kMBwd | kMRng, kMBwd | kMJ4 | kMSwap | kMSum>, grid, dim3(kFgThreads), lds,
+                      (hipStream_t)stream, a, b);
     else {   // any other pair of option words: the two stages as two launches (the same bits; a generic two-stage image would not fit 256 registers)
         if (int rc = fg_launch(a, 256, 1, (hipStream_t)stream)) return rc;
         return fg_launch(b, 256, 1, (hipStream_t)stream);
     }
-    return check_launch("ff_gemm_act2_kernel");
 }
 
 int vlg_ff_linear_kn(const void* x, int ldx, const void* w, int ldw, long long rows, int ncols, const uint64_t* rng, unsigned site, float p, void* out, int ldo,
@@ -650,8 +636,7 @@ int vlg_ff_transpose256(const void* const* w, int n, void* out, void* stream) {
         if (!w[z]) return set_error(VLG_ERR_ARG, "ff_transpose256: matrix %d is null", z);
         a.w[z] = (const uint16_t*)w[z];
     }
-    hipLaunchKernelGGL(ff_transpose256_kernel, dim3(8, 8, n), dim3(256), 0, (hipStream_t)stream, a, (uint16_t*)out);
-    return check_launch("ff_transpose256_kernel");
+    return launch("ff_transpose256_kernel", ff_transpose256_kernel, dim3(8, 8, n), dim3(256), 0, (hipStream_t)stream, a, (uint16_t*)out);
 }
 
 }  // extern "C"

@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "vlg_common.h"
+#include "vlg_launch.h"
 #include "vlg_mfma.h"
 
 namespace vlg {
@@ -838,12 +839,14 @@ int vlg_linear_wgrad_partial_group(const VlgWgradPartial* items, int count, void
         TnGroup& g = grp[c];
         if (g.count == 0) return 0;
         const dim3 grid(g.start[g.count]);
-        if (c == 0) hipLaunchKernelGGL((gemm_tn_group_kernel<64, VLG_TN64_STAGE, VLG_TN64_SETS, true, true>), grid, dim3(kGemmThreads), 0, s, g);
-        else if (c == 1) hipLaunchKernelGGL((gemm_tn_group_kernel<128, VLG_TN128_STAGE, VLG_TN128_SETS, true, false>), grid, dim3(kGemmThreads), 0, s, g);
-        else if (c == 2) hipLaunchKernelGGL((gemm_tn_group_kernel<128, VLG_TN128_STAGE, VLG_TN128_SETS, false, true>), grid, dim3(kGemmThreads), 0, s, g);
-        else hipLaunchKernelGGL((gemm_tn_group_kernel<128, VLG_TN128_STAGE, VLG_TN128_SETS, false, false>), grid, dim3(kGemmThreads), 0, s, g);
+        auto go = [&](auto k) { return launch("gemm_tn_group_kernel", k, grid, dim3(kGemmThreads), 0, s, g); };
+        if (int rc = c == 0   ? go(gemm_tn_group_kernel<64, VLG_TN64_STAGE, VLG_TN64_SETS, true, true>)
+                     : c == 1 ? go(gemm_tn_group_kernel<128, VLG_TN128_STAGE, VLG_TN128_SETS, true, false>)
+                     : c == 2 ? go(gemm_tn_group_kernel<128, VLG_TN128_STAGE, VLG_TN128_SETS, false, true>)
+                              : go(gemm_tn_group_kernel<128, VLG_TN128_STAGE, VLG_TN128_SETS, false, false>))
+            return rc;
         g.count = 0;
-        return check_launch("gemm_tn_group_kernel");
+        return 0;
     };
     for (int i = 0; i < count; ++i) {
         const VlgWgradPartial& q = items[i];
@@ -896,8 +899,7 @@ int vlg_linear_wgrad_reduce_group(const VlgWgradReduce* items, int count, void* 
             g.blocks += (a.n + a.n_cs + a.n_csb + 255) / 256;
         }
         if (g.count == 0) continue;
-        hipLaunchKernelGGL(gemm_reduce_group_kernel, dim3(g.blocks), dim3(256), 0, s, g);
-        if (int rc = check_launch("gemm_reduce_group_kernel")) return rc;
+        if (int rc = launch("gemm_reduce_group_kernel", gemm_reduce_group_kernel, dim3(g.blocks), dim3(256), 0, s, g)) return rc;
     }
     return 0;
 }
@@ -928,31 +930,30 @@ static int wgrad_launch(const void* dy, int ld_dy, const void* x, int ld_x, int 
     const int kTile = big ? 128 : 64;
     const int tiles = ((M + kTile - 1) / kTile) * ((N + kTile - 1) / kTile);
     const dim3 grid(tiles * ((pl.S + 7) / 8) * 8);
-#define VLG_TN(...) hipLaunchKernelGGL((gemm_tn_kernel<__VA_ARGS__>), grid, dim3(kGemmThreads), 0, s, (const uint16_t*)dy, ld_dy, (const uint16_t*)x, ld_x, K, M, N, \
+#define VLG_TN(...) launch("gemm_tn_kernel", gemm_tn_kernel<__VA_ARGS__>, grid, dim3(kGemmThreads), 0, s, (const uint16_t*)dy, ld_dy, (const uint16_t*)x, ld_x, K, M, N, \
                                        pl.KC, pl.S, part, part_cs, part_csb)
-#define VLG_TN3(...) hipLaunchKernelGGL((gemm_tn3_kernel<__VA_ARGS__>), grid, dim3(kGemmThreads), 0, s, (const float*)dy, ld_dy, (const float*)x, ld_x, K, M, N, \
+#define VLG_TN3(...) launch("gemm_tn3_kernel", gemm_tn3_kernel<__VA_ARGS__>, grid, dim3(kGemmThreads), 0, s, (const float*)dy, ld_dy, (const float*)x, ld_x, K, M, N, \
                                         pl.KC, pl.S, part, part_cs, part_csb)
-    if (f32) {   // float32 operands: three bf16 products per pair (gemm_tn3_kernel)
-        if (!big) VLG_TN3(64, 64, true, true);
-        else if (d_bias) VLG_TN3(128, 32, true, false);
-        else if (x_colsum) VLG_TN3(128, 32, false, true);
-        else VLG_TN3(128, 32, false, false);
-    } else if (!big) VLG_TN(64, VLG_TN64_STAGE, VLG_TN64_SETS, true, true);
-    else if (d_bias) VLG_TN(128, VLG_TN128_STAGE, VLG_TN128_SETS, true, false);
-    else if (x_colsum) VLG_TN(128, VLG_TN128_STAGE, VLG_TN128_SETS, false, true);
-    else VLG_TN(128, VLG_TN128_STAGE, VLG_TN128_SETS, false, false);
+    // float32 operands: three bf16 products per pair (gemm_tn3_kernel)
+    if (int rc = f32 ? (!big       ? VLG_TN3(64, 64, true, true)
+                        : d_bias   ? VLG_TN3(128, 32, true, false)
+                        : x_colsum ? VLG_TN3(128, 32, false, true)
+                                   : VLG_TN3(128, 32, false, false))
+                     : (!big       ? VLG_TN(64, VLG_TN64_STAGE, VLG_TN64_SETS, true, true)
+                        : d_bias   ? VLG_TN(128, VLG_TN128_STAGE, VLG_TN128_SETS, true, false)
+                        : x_colsum ? VLG_TN(128, VLG_TN128_STAGE, VLG_TN128_SETS, false, true)
+                                   : VLG_TN(128, VLG_TN128_STAGE, VLG_TN128_SETS, false, false)))
+        return rc;
 #undef VLG_TN
 #undef VLG_TN3
-    if (int rc = check_launch("gemm_tn_kernel")) return rc;
     if (!reduce_now) return 0;
     const int n = M * N, n_cs = d_bias ? M : 0, n_csb = x_colsum ? N : 0;
     if (out_dtype == VLG_F32)
-        hipLaunchKernelGGL(gemm_reduce_kernel<float>, dim3((n + n_cs + n_csb + 255) / 256), dim3(256), 0, s, part, pl.S, n, N, ld_dw, (float*)d_weight, part_cs,
-                           n_cs, (float*)d_bias, part_csb, n_csb, (float*)x_colsum);
+        return launch("gemm_reduce_kernel", gemm_reduce_kernel<float>, dim3((n + n_cs + n_csb + 255) / 256), dim3(256), 0, s, part, pl.S, n, N, ld_dw,
+                      (float*)d_weight, part_cs, n_cs, (float*)d_bias, part_csb, n_csb, (float*)x_colsum);
     else
-        hipLaunchKernelGGL(gemm_reduce_kernel<uint16_t>, dim3((n + n_cs + n_csb + 255) / 256), dim3(256), 0, s, part, pl.S, n, N, ld_dw, (uint16_t*)d_weight,
-                           part_cs, n_cs, (uint16_t*)d_bias, part_csb, n_csb, (uint16_t*)x_colsum);
-    return check_launch("gemm_reduce_kernel");
+        return launch("gemm_reduce_kernel", gemm_reduce_kernel<uint16_t>, dim3((n + n_cs + n_csb + 255) / 256), dim3(256), 0, s, part, pl.S, n, N, ld_dw,
+                      (uint16_t*)d_weight, part_cs, n_cs, (uint16_t*)d_bias, part_csb, n_csb, (uint16_t*)x_colsum);
 }
 
 static int sg_make(vlg::SgArgs& p, const void* a, long long sab, long long sam, long long sak, const void* b, long long sbb, long long sbk, long long sbn,
@@ -1005,8 +1006,7 @@ int vlg_small_gemm_group(const VlgSmallGemm* problems, int count, void* stream) 
         }
         if (gp.count == 0) continue;
         gp.start[gp.count] = blocks;
-        hipLaunchKernelGGL(small_gemm_group_kernel, dim3(blocks), dim3(64), 0, s, gp);
-        if (int rc = check_launch("small_gemm_group_kernel")) return rc;
+        if (int rc = launch("small_gemm_group_kernel", small_gemm_group_kernel, dim3(blocks), dim3(64), 0, s, gp)) return rc;
     }
     return 0;
 }
@@ -1021,11 +1021,10 @@ int vlg_small_gemm(const void* a, long long sab, long long sam, long long sak, c
     if (batch == 0) return 0;
     const dim3 grid(((M + 31) / 32) * ((N + 31) / 32), batch);
     hipStream_t s = (hipStream_t)stream;
-    if (in_dtype == VLG_F32 && out_dtype == VLG_F32) hipLaunchKernelGGL((small_gemm_kernel<true, float>), grid, dim3(64), 0, s, p);
-    else if (in_dtype == VLG_F32) hipLaunchKernelGGL((small_gemm_kernel<true, uint16_t>), grid, dim3(64), 0, s, p);
-    else if (out_dtype == VLG_F32) hipLaunchKernelGGL((small_gemm_kernel<false, float>), grid, dim3(64), 0, s, p);
-    else hipLaunchKernelGGL((small_gemm_kernel<false, uint16_t>), grid, dim3(64), 0, s, p);
-    return check_launch("small_gemm_kernel");
+    if (in_dtype == VLG_F32 && out_dtype == VLG_F32) return launch("small_gemm_kernel", small_gemm_kernel<true, float>, grid, dim3(64), 0, s, p);
+    else if (in_dtype == VLG_F32) return launch("small_gemm_kernel", small_gemm_kernel<true, uint16_t>, grid, dim3(64), 0, s, p);
+    else if (out_dtype == VLG_F32) return launch("small_gemm_kernel", small_gemm_kernel<false, float>, grid, dim3(64), 0, s, p);
+    else return launch("small_gemm_kernel", small_gemm_kernel<false, uint16_t>, grid, dim3(64), 0, s, p);
 }
 
 }  // extern "C"

@@ -25,6 +25,7 @@
 #include <algorithm>
 
 #include "vlg_common.h"
+#include "vlg_launch.h"
 #include "vlg_dp_core.h"   // F32In / BF16In element loaders
 #include "vlg_ground.h"
 
@@ -571,12 +572,9 @@ static int launch_bwd(const void* txt, const void* vis, const float* gV, const u
         // register slots pay off up to 3 rows per wave; with 6 the per-lane selects cost more than the LDS round trips
         if (side == 0) k = coop ? ground_bwd_kernel<In, true, 0, true> : rows <= 48 ? ground_bwd_kernel<In, true, 3> : ground_bwd_kernel<In, true, 0>;
         else k = coop ? ground_bwd_kernel<In, false, 0, true> : rows <= 48 ? ground_bwd_kernel<In, false, 3> : ground_bwd_kernel<In, false, 0>;
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return set_error((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        }
-        hipLaunchKernelGGL(k, dim3(B, (rows + rpb - 1) / rpb), dim3(64 * kGbWaves), lds, s, (P)txt, (P)vis, gV, argV, gQ, argQ, coef,
-                           B, Q, V, d, rpb, out);
+        if (int rc = launch("ground_bwd_kernel", k, dim3(B, (rows + rpb - 1) / rpb), dim3(64 * kGbWaves), lds, s, (P)txt, (P)vis, gV, argV, gQ, argQ, coef, B,
+                            Q, V, d, rpb, out))
+            return rc;
     }
     return 0;
 }
@@ -1302,43 +1300,39 @@ static int launch_bwd_dense(const void* txt, const void* vis, const float* gV, c
         const int kt = (pp * uw + 31) / 32 * 32, chp = pp == 3 ? 6 : kGdChunk;
         return 2 * (size_t)(kGdD + mt * 16) * (kt * 2 + 32) + 2 * (size_t)chp * (mt * 16 + Kp) * (2 + 4);
     };
-#define VLG_WS(SIDEV, NKCV, MTV, RWV, SEGV, PPV, UWV, FT, OUT)                                                          \
-    do {                                                                                                               \
-        auto kern = ground_bwd_ws_kernel<SIDEV, NKCV, MTV, RWV, SEGV, PPV, UWV, (SIDEV == 1 && RWV == 1 ? 2 : 1)>;        \
-        const size_t nb = lds_ws(NKCV * 32, MTV, PPV, UWV);                                                            \
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)nb);    \
-        if (e != hipSuccess) return set_error((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));                \
-        hipLaunchKernelGGL(kern, dim3(B, 1), dim3(kGwThreads), nb, s, FT, gV, argV, gQ, argQ, coef, B, Q, V, OUT);             \
-    } while (0)
-#define VLG_WS0(MTV, RWV)                                                                                              \
-    do { if (V <= 40) VLG_WS(0, 2, MTV, RWV, 5, 3, 40, visT, g_txt); else VLG_WS(0, 2, MTV, RWV, 8, 2, 64, visT, g_txt); } while (0)
+#define VLG_WS(SIDEV, NKCV, MTV, RWV, SEGV, PPV, UWV, FT, OUT)                                                                                   \
+    launch("ground_bwd_ws_kernel", ground_bwd_ws_kernel<SIDEV, NKCV, MTV, RWV, SEGV, PPV, UWV, (SIDEV == 1 && RWV == 1 ? 2 : 1)>, dim3(B, 1),    \
+           dim3(kGwThreads), lds_ws(NKCV * 32, MTV, PPV, UWV), s, FT, gV, argV, gQ, argQ, coef, B, Q, V, OUT)
+#define VLG_WS0(MTV, RWV) (V <= 40 ? VLG_WS(0, 2, MTV, RWV, 5, 3, 40, visT, g_txt) : VLG_WS(0, 2, MTV, RWV, 8, 2, 64, visT, g_txt))
     const bool both_ws = g_txt && g_vis && V <= 48;
     if (both_ws) {
-        hipLaunchKernelGGL(ground_transpose2_kernel, dim3(B, KtV / 32 + KpQ / 32), dim3(256), 0, s, (const uint16_t*)vis, V, KtV, visT, KtV / 32,
-                           (const uint16_t*)txt, Q, KpQ, txtT);
-        if (int rc = check_launch("ground_transpose2_kernel")) return rc;
+        if (int rc = launch("ground_transpose2_kernel", ground_transpose2_kernel, dim3(B, KtV / 32 + KpQ / 32), dim3(256), 0, s, (const uint16_t*)vis, V, KtV,
+                            visT, KtV / 32, (const uint16_t*)txt, Q, KpQ, txtT))
+            return rc;
     }
     if (g_txt && !wide) {
-        if (!both_ws) hipLaunchKernelGGL(ground_transpose_kernel, dim3(B, KtV / 32), dim3(256), 0, s, (const uint16_t*)vis, V, KtV, visT);
-        switch ((Q + 15) / 16) {
-            case 1: VLG_WS0(1, 1); break;
-            case 2: VLG_WS0(2, 2); break;
-            case 3: VLG_WS0(3, 1); break;
-            case 4: VLG_WS0(4, 2); break;
-            case 5: VLG_WS0(5, 2); break;
-            default: VLG_WS0(6, 2); break;
-        }
-        if (int rc = check_launch("ground_bwd_ws_kernel")) return rc;
+        if (!both_ws)
+            if (int rc = launch("ground_transpose_kernel", ground_transpose_kernel, dim3(B, KtV / 32), dim3(256), 0, s, (const uint16_t*)vis, V, KtV, visT))
+                return rc;
+        const int mt = (Q + 15) / 16;   // query tiles
+        if (int rc = mt == 1   ? VLG_WS0(1, 1)
+                     : mt == 2 ? VLG_WS0(2, 2)
+                     : mt == 3 ? VLG_WS0(3, 1)
+                     : mt == 4 ? VLG_WS0(4, 2)
+                     : mt == 5 ? VLG_WS0(5, 2)
+                               : VLG_WS0(6, 2))
+            return rc;
         g_txt = nullptr;
     }
     if (g_vis && V <= 48) {   // (four region tiles: the double buffers do not fit the LDS)
-        if (!both_ws) hipLaunchKernelGGL(ground_transpose_kernel, dim3(B, KpQ / 32), dim3(256), 0, s, (const uint16_t*)txt, Q, KpQ, txtT);
-        switch ((V + 15) / 16) {
-            case 1: VLG_WS(1, 3, 1, 1, 12, 2, 96, txtT, g_vis); break;
-            case 2: VLG_WS(1, 3, 2, 2, 12, 2, 96, txtT, g_vis); break;
-            default: VLG_WS(1, 3, 3, 1, 12, 2, 96, txtT, g_vis); break;
-        }
-        if (int rc = check_launch("ground_bwd_ws_kernel")) return rc;
+        if (!both_ws)
+            if (int rc = launch("ground_transpose_kernel", ground_transpose_kernel, dim3(B, KpQ / 32), dim3(256), 0, s, (const uint16_t*)txt, Q, KpQ, txtT))
+                return rc;
+        const int mt = (V + 15) / 16;   // region tiles
+        if (int rc = mt == 1   ? VLG_WS(1, 3, 1, 1, 12, 2, 96, txtT, g_vis)
+                     : mt == 2 ? VLG_WS(1, 3, 2, 2, 12, 2, 96, txtT, g_vis)
+                               : VLG_WS(1, 3, 3, 1, 12, 2, 96, txtT, g_vis))
+            return rc;
         g_vis = nullptr;
     }
 #undef VLG_WS0
@@ -1358,30 +1352,28 @@ static int launch_bwd_dense(const void* txt, const void* vis, const float* gV, c
         if (e == hipSuccess && g_vis && split > 1 && !wide) e = hipMemsetAsync(g_vis, 0, sizeof(float) * (size_t)B * V * kGdD, s);
         if (e != hipSuccess) return set_error((int)e, "hipMemsetAsync: %s", hipGetErrorString(e));
     }
-#define VLG_GD2(SIDEV, NKCV, MTV, RWV, SEGV, PPV, GRID, KTOT, NKC_RT, STRIDE, FT, OUT)                                  \
-    do {                                                                                                               \
-        auto kern = ground_bwd_dense_kernel<SIDEV, NKCV, MTV, RWV, SEGV, PPV>;                                         \
-        const size_t nb = lds(NKCV * 32, MTV, PPV);                                                                    \
-        if (nb > 64 * 1024) {                                                                                          \
-            hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)nb); \
-            if (e != hipSuccess) return set_error((int)e, "hipFuncSetAttribute: %s", hipGetErrorString(e));            \
-        }                                                                                                              \
-        hipLaunchKernelGGL(kern, GRID, dim3(256), nb, s, FT, gV, argV, gQ, argQ, coef, B, Q, V, KTOT, NKC_RT, (size_t)(STRIDE), OUT); \
-    } while (0)
+#define VLG_GD2(SIDEV, NKCV, MTV, RWV, SEGV, PPV, GRID, KTOT, NKC_RT, STRIDE, FT, OUT)                                                     \
+    launch("ground_bwd_dense_kernel", ground_bwd_dense_kernel<SIDEV, NKCV, MTV, RWV, SEGV, PPV>, GRID, dim3(256), lds(NKCV * 32, MTV, PPV), s, FT, gV, \
+           argV, gQ, argQ, coef, B, Q, V, KTOT, NKC_RT, (size_t)(STRIDE), OUT)
     if (g_txt) {   // (wide) rows = queries (Q <= 96), contraction over regions
-        hipLaunchKernelGGL(ground_transpose_kernel, dim3(B, KtV / 32), dim3(256), 0, s, (const uint16_t*)vis, V, KtV, visT);
+        if (int rc = launch("ground_transpose_kernel", ground_transpose_kernel, dim3(B, KtV / 32), dim3(256), 0, s, (const uint16_t*)vis, V, KtV, visT))
+            return rc;
         float* dst = part_txt ? partial : g_txt;
-        VLG_GD2(0, 4, 6, 2, 16, 1, dim3(B, split_txt), KtV, n_kc_v, part_txt ? (size_t)B * Q * kGdD : 0, visT, dst);
+        if (int rc = VLG_GD2(0, 4, 6, 2, 16, 1, dim3(B, split_txt), KtV, n_kc_v, part_txt ? (size_t)B * Q * kGdD : 0, visT, dst)) return rc;
         if (part_txt) {
             const size_t n4 = (size_t)B * Q * kGdD / 4;
-            hipLaunchKernelGGL(ground_partial_sum_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, partial, split_txt, n4,
-                               g_txt);
+            if (int rc = launch("ground_partial_sum_kernel", ground_partial_sum_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, partial, split_txt,
+                                n4, g_txt))
+                return rc;
         }
     }
     if (g_vis) {   // rows = regions, contraction over queries (Q <= 96)
-        hipLaunchKernelGGL(ground_transpose_kernel, dim3(B, KpQ / 32), dim3(256), 0, s, (const uint16_t*)txt, Q, KpQ, txtT);
-        if (wide) VLG_GD2(1, 3, 6, 2, 12, 1, dim3(B, 1, (V + 95) / 96), KpQ, 1, 0, txtT, g_vis);   // one pair per step: two blocks fit a CU's LDS
-        else VLG_GD2(1, 3, 4, 2, 12, 2, dim3(B, split), KpQ, 1, 0, txtT, g_vis);                 // 48 < V <= 64: four region tiles, two pairs per step
+        if (int rc = launch("ground_transpose_kernel", ground_transpose_kernel, dim3(B, KpQ / 32), dim3(256), 0, s, (const uint16_t*)txt, Q, KpQ, txtT))
+            return rc;
+        // wide: one pair per step, two blocks fit a CU's LDS; 48 < V <= 64: four region tiles, two pairs per step
+        if (int rc = wide ? VLG_GD2(1, 3, 6, 2, 12, 1, dim3(B, 1, (V + 95) / 96), KpQ, 1, 0, txtT, g_vis)
+                          : VLG_GD2(1, 3, 4, 2, 12, 2, dim3(B, split), KpQ, 1, 0, txtT, g_vis))
+            return rc;
     }
 #undef VLG_GD2
     return 0;
@@ -1436,8 +1428,7 @@ ReducedPlan::ReducedPlan(int B, int Q) {
 }
 
 int launch_reduced_logit(const float* maxV, const float* marg, int B, int Q, float* sums, float* logit, hipStream_t s) {
-    hipLaunchKernelGGL(reduced_logit_kernel, dim3(B), dim3(256), 0, s, maxV, marg, B, Q, sums, logit);
-    return check_launch("reduced_logit_kernel");
+    return launch("reduced_logit_kernel", reduced_logit_kernel, dim3(B), dim3(256), 0, s, maxV, marg, B, Q, sums, logit);
 }
 
 int launch_reduced_backward(const void* txt, const void* vis, const uint8_t* tmask, const uint8_t* vmask, const float* marg,
@@ -1446,13 +1437,12 @@ int launch_reduced_backward(const void* txt, const void* vis, const uint8_t* tma
     float *gV = ws + p.off_gV, *coef = ws + p.off_coef;
     const uint16_t* aV = reinterpret_cast<const uint16_t*>(ws + p.off_argV);
     const size_t n = (size_t)B * B * Q;
-    hipLaunchKernelGGL(reduced_coef_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65535)), dim3(256), 0, s, g_logit, marg,
-                       ws + p.off_sum, aV, tmask, vmask, B, Q, V, gV, coef);
+    if (int rc = launch("reduced_coef_kernel", reduced_coef_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65535)), dim3(256), 0, s, g_logit, marg,
+                        ws + p.off_sum, aV, tmask, vmask, B, Q, V, gV, coef))
+        return rc;
     // the max-over-Q arrays are never read (their factor coef[1] is 0): any valid pointers do
-    const int rc = in_dtype == VLG_F32 ? launch_bwd<F32In>(txt, vis, gV, aV, gV, aV, coef, B, Q, V, d, g_txt, g_vis, s, false)
-                                       : launch_bwd<BF16In>(txt, vis, gV, aV, gV, aV, coef, B, Q, V, d, g_txt, g_vis, s, false);
-    if (rc) return rc;
-    return check_launch("align_reduced_backward");
+    return in_dtype == VLG_F32 ? launch_bwd<F32In>(txt, vis, gV, aV, gV, aV, coef, B, Q, V, d, g_txt, g_vis, s, false)
+                               : launch_bwd<BF16In>(txt, vis, gV, aV, gV, aV, coef, B, Q, V, d, g_txt, g_vis, s, false);
 }
 
 GroundPlan::GroundPlan(int B, int Q, int V) {
@@ -1506,21 +1496,20 @@ int launch_grounding_tail(const void* txt, const void* vis, const uint8_t* tmask
     // null = all ones); gate: vmask[a][v], tmask[b][argQ]
     if (tiled) {
         const size_t lds2 = std::max(s1.lds, s2.lds);
-        if (lds2 > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void*)ground_ce_tile2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-            if (e != hipSuccess) return set_error((int)e, "grounding_loss: hipFuncSetAttribute(%zu): %s", lds2, hipGetErrorString(e));
-        }
         const CeSide sa{mV, (size_t)B * Q, (size_t)Q, Q, s1.cw, marg, aV, tmask, vmask, V, part, y1};
         const CeSide sb{mQ, (size_t)V, (size_t)B * V, V, s2.cw, vmask, aQ, vmask, tmask, Q, part2, y2};
-        hipLaunchKernelGGL(ground_ce_tile2_kernel, dim3(B, y1 + y2), dim3(kCeTileThreads), lds2, s, B, sa, sb);
+        if (int rc = launch("ground_ce_tile2_kernel", ground_ce_tile2_kernel, dim3(B, y1 + y2), dim3(kCeTileThreads), lds2, s, B, sa, sb)) return rc;
     } else {   // a strip does not fit the LDS tile or the block: the streaming kernel, one launch per direction
-        hipLaunchKernelGGL(ground_ce_kernel<float>, dim3(B, y1), dim3(kCeThreads), 0, s, mV, (size_t)B * Q, (size_t)Q, B, Q, marg, aV,
-                           tmask, vmask, V, part);
-        hipLaunchKernelGGL(ground_ce_kernel<uint8_t>, dim3(B, y2), dim3(kCeThreads), 0, s, mQ, (size_t)V, (size_t)B * V, B, V, vmask, aQ,
-                           vmask, tmask, Q, part2);
+        if (int rc = launch("ground_ce_kernel", ground_ce_kernel<float>, dim3(B, y1), dim3(kCeThreads), 0, s, mV, (size_t)B * Q, (size_t)Q, B, Q, marg, aV,
+                            tmask, vmask, V, part))
+            return rc;
+        if (int rc = launch("ground_ce_kernel", ground_ce_kernel<uint8_t>, dim3(B, y2), dim3(kCeThreads), 0, s, mQ, (size_t)V, (size_t)B * V, B, V, vmask, aQ,
+                            vmask, tmask, Q, part2))
+            return rc;
     }
-    hipLaunchKernelGGL(ground_sum_kernel, dim3(1), dim3(64), 0, s, part, part2, B * y1, B * y2, num_token, num_token_dev, w_v2t, out_sums,
-                       coef);
+    if (int rc = launch("ground_sum_kernel", ground_sum_kernel, dim3(1), dim3(64), 0, s, part, part2, B * y1, B * y2, num_token, num_token_dev, w_v2t, out_sums,
+                        coef))
+        return rc;
     if ((g_txt || g_vis) && in_dtype == VLG_BF16 && d == kGdD && Q <= 96 && V <= 65535) {
         // bf16 features, d = 128, up to 96 queries: the dense route on the matrix cores
         if (int rc = launch_bwd_dense(txt, vis, mV, aV, mQ, aQ, coef, B, Q, V, reinterpret_cast<uint16_t*>(ws + p.off_featT),
@@ -1531,7 +1520,7 @@ int launch_grounding_tail(const void* txt, const void* vis, const uint8_t* tmask
                                            : launch_bwd<BF16In>(txt, vis, mV, aV, mQ, aQ, coef, B, Q, V, d, g_txt, g_vis, s, w_v2t > 0.f);
         if (rc) return rc;
     }
-    return check_launch("grounding_loss");
+    return 0;
 }
 
 }  // namespace vlg

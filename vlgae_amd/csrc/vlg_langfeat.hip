@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "vlg_common.h"
+#include "vlg_launch.h"
 #include "vlg_rows.h"
 
 namespace vlg {
@@ -250,7 +251,7 @@ inline bool ok_dtype(int t) { return t == VLG_F32 || t == VLG_BF16; }
 
 namespace {
 template <typename A>
-void launch_split_bwd(const void* d_txt, bool t32, const float* d_child, const float* d_parent, const void* d_sum, bool s32,
+int launch_split_bwd(const void* d_txt, bool t32, const float* d_child, const float* d_parent, const void* d_sum, bool s32,
                       const void* child, const void* parent, const int64_t* heads, const float* drop, int ld_drop, int B, int N, int d, float slope,
                       void* d_pre, hipStream_t s) {
     using namespace vlg;
@@ -259,13 +260,17 @@ void launch_split_bwd(const void* d_txt, bool t32, const float* d_child, const f
     A* o = (A*)d_pre;
     const dim3 grid(B), block(kSplitBwdThreads);
     if (t32 && s32)
-        hipLaunchKernelGGL((langfeat_split_bwd_kernel<float, float, A>), grid, block, lds, s, (const float*)d_txt, d_child, d_parent, (const float*)d_sum, c, p, heads, drop, ld_drop, N, d, slope, o);
+        return launch("langfeat_split_bwd_kernel", langfeat_split_bwd_kernel<float, float, A>, grid, block, lds, s, (const float*)d_txt, d_child, d_parent,
+                      (const float*)d_sum, c, p, heads, drop, ld_drop, N, d, slope, o);
     else if (t32)
-        hipLaunchKernelGGL((langfeat_split_bwd_kernel<float, uint16_t, A>), grid, block, lds, s, (const float*)d_txt, d_child, d_parent, (const uint16_t*)d_sum, c, p, heads, drop, ld_drop, N, d, slope, o);
+        return launch("langfeat_split_bwd_kernel", langfeat_split_bwd_kernel<float, uint16_t, A>, grid, block, lds, s, (const float*)d_txt, d_child, d_parent,
+                      (const uint16_t*)d_sum, c, p, heads, drop, ld_drop, N, d, slope, o);
     else if (s32)
-        hipLaunchKernelGGL((langfeat_split_bwd_kernel<uint16_t, float, A>), grid, block, lds, s, (const uint16_t*)d_txt, d_child, d_parent, (const float*)d_sum, c, p, heads, drop, ld_drop, N, d, slope, o);
+        return launch("langfeat_split_bwd_kernel", langfeat_split_bwd_kernel<uint16_t, float, A>, grid, block, lds, s, (const uint16_t*)d_txt, d_child,
+                      d_parent, (const float*)d_sum, c, p, heads, drop, ld_drop, N, d, slope, o);
     else
-        hipLaunchKernelGGL((langfeat_split_bwd_kernel<uint16_t, uint16_t, A>), grid, block, lds, s, (const uint16_t*)d_txt, d_child, d_parent, (const uint16_t*)d_sum, c, p, heads, drop, ld_drop, N, d, slope, o);
+        return launch("langfeat_split_bwd_kernel", langfeat_split_bwd_kernel<uint16_t, uint16_t, A>, grid, block, lds, s, (const uint16_t*)d_txt, d_child,
+                      d_parent, (const uint16_t*)d_sum, c, p, heads, drop, ld_drop, N, d, slope, o);
 }
 }  // namespace
 
@@ -281,14 +286,13 @@ int vlg_langfeat_root_cat(const void* x, const int64_t* lengths, int B, int L, i
     const dim3 grid(B, (h + 255) / 256);
     hipStream_t s = (hipStream_t)stream;
     if (in_dtype == VLG_F32 && out_dtype == VLG_F32)
-        hipLaunchKernelGGL((langfeat_x1_kernel<float, float>), grid, dim3(256), 0, s, (const float*)x, lengths, L, h, (float*)x1);
+        return launch("langfeat_x1_kernel", langfeat_x1_kernel<float, float>, grid, dim3(256), 0, s, (const float*)x, lengths, L, h, (float*)x1);
     else if (in_dtype == VLG_F32)
-        hipLaunchKernelGGL((langfeat_x1_kernel<float, uint16_t>), grid, dim3(256), 0, s, (const float*)x, lengths, L, h, (uint16_t*)x1);
+        return launch("langfeat_x1_kernel", langfeat_x1_kernel<float, uint16_t>, grid, dim3(256), 0, s, (const float*)x, lengths, L, h, (uint16_t*)x1);
     else if (out_dtype == VLG_F32)
-        hipLaunchKernelGGL((langfeat_x1_kernel<uint16_t, float>), grid, dim3(256), 0, s, (const uint16_t*)x, lengths, L, h, (float*)x1);
+        return launch("langfeat_x1_kernel", langfeat_x1_kernel<uint16_t, float>, grid, dim3(256), 0, s, (const uint16_t*)x, lengths, L, h, (float*)x1);
     else
-        hipLaunchKernelGGL((langfeat_x1_kernel<uint16_t, uint16_t>), grid, dim3(256), 0, s, (const uint16_t*)x, lengths, L, h, (uint16_t*)x1);
-    return check_launch("langfeat_x1_kernel");
+        return launch("langfeat_x1_kernel", langfeat_x1_kernel<uint16_t, uint16_t>, grid, dim3(256), 0, s, (const uint16_t*)x, lengths, L, h, (uint16_t*)x1);
 }
 
 int vlg_langfeat_root_cat_backward(const void* d_x1, const int64_t* lengths, int B, int L, int h, int in_dtype, void* d_x, int out_dtype,
@@ -301,14 +305,16 @@ int vlg_langfeat_root_cat_backward(const void* d_x1, const int64_t* lengths, int
     const dim3 grid(B, (h + 255) / 256);
     hipStream_t s = (hipStream_t)stream;
     if (in_dtype == VLG_F32 && out_dtype == VLG_F32)
-        hipLaunchKernelGGL((langfeat_x1_bwd_kernel<float, float>), grid, dim3(256), 0, s, (const float*)d_x1, lengths, L, h, (float*)d_x);
+        return launch("langfeat_x1_bwd_kernel", langfeat_x1_bwd_kernel<float, float>, grid, dim3(256), 0, s, (const float*)d_x1, lengths, L, h, (float*)d_x);
     else if (in_dtype == VLG_F32)
-        hipLaunchKernelGGL((langfeat_x1_bwd_kernel<float, uint16_t>), grid, dim3(256), 0, s, (const float*)d_x1, lengths, L, h, (uint16_t*)d_x);
+        return launch("langfeat_x1_bwd_kernel", langfeat_x1_bwd_kernel<float, uint16_t>, grid, dim3(256), 0, s, (const float*)d_x1, lengths, L, h,
+                      (uint16_t*)d_x);
     else if (out_dtype == VLG_F32)
-        hipLaunchKernelGGL((langfeat_x1_bwd_kernel<uint16_t, float>), grid, dim3(256), 0, s, (const uint16_t*)d_x1, lengths, L, h, (float*)d_x);
+        return launch("langfeat_x1_bwd_kernel", langfeat_x1_bwd_kernel<uint16_t, float>, grid, dim3(256), 0, s, (const uint16_t*)d_x1, lengths, L, h,
+                      (float*)d_x);
     else
-        hipLaunchKernelGGL((langfeat_x1_bwd_kernel<uint16_t, uint16_t>), grid, dim3(256), 0, s, (const uint16_t*)d_x1, lengths, L, h, (uint16_t*)d_x);
-    return check_launch("langfeat_x1_bwd_kernel");
+        return launch("langfeat_x1_bwd_kernel", langfeat_x1_bwd_kernel<uint16_t, uint16_t>, grid, dim3(256), 0, s, (const uint16_t*)d_x1, lengths, L, h,
+                      (uint16_t*)d_x);
 }
 
 int vlg_langfeat_split(const void* pre, const int64_t* heads, const float* drop, int ld_drop, int B, int N, int d, int act_dtype, float slope,
@@ -322,12 +328,11 @@ int vlg_langfeat_split(const void* pre, const int64_t* heads, const float* drop,
     const size_t threads = (size_t)B * N * (d / 8);
     const dim3 grid((unsigned)((threads + 255) / 256));
     if (act_dtype == VLG_F32)
-        hipLaunchKernelGGL(langfeat_split_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)pre, heads, drop, ld_drop, B, N, d,
-                           slope, (float*)txt, (float*)child, (float*)parent, (float*)sum);
+        return launch("langfeat_split_kernel", langfeat_split_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)pre, heads, drop, ld_drop,
+                      B, N, d, slope, (float*)txt, (float*)child, (float*)parent, (float*)sum);
     else
-        hipLaunchKernelGGL(langfeat_split_kernel<uint16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)pre, heads, drop, ld_drop, B, N,
-                           d, slope, (uint16_t*)txt, (uint16_t*)child, (uint16_t*)parent, (uint16_t*)sum);
-    return check_launch("langfeat_split_kernel");
+        return launch("langfeat_split_kernel", langfeat_split_kernel<uint16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)pre, heads, drop,
+                      ld_drop, B, N, d, slope, (uint16_t*)txt, (uint16_t*)child, (uint16_t*)parent, (uint16_t*)sum);
 }
 
 int vlg_langfeat_split_backward(const void* d_txt, int d_txt_dtype, const float* d_child, const float* d_parent, const void* d_sum,
@@ -343,10 +348,8 @@ int vlg_langfeat_split_backward(const void* d_txt, int d_txt_dtype, const float*
     if (drop && ld_drop < 3 * d) return set_error(VLG_ERR_SHAPE, "langfeat_split_backward: ld_drop=%d < 3d", ld_drop);
     const bool t32 = d_txt_dtype == VLG_F32, s32 = !d_sum || d_sum_dtype == VLG_F32;
     if (act_dtype == VLG_F32)
-        launch_split_bwd<float>(d_txt, t32, d_child, d_parent, d_sum, s32, child, parent, heads, drop, ld_drop, B, N, d, slope, d_pre, (hipStream_t)stream);
-    else
-        launch_split_bwd<uint16_t>(d_txt, t32, d_child, d_parent, d_sum, s32, child, parent, heads, drop, ld_drop, B, N, d, slope, d_pre, (hipStream_t)stream);
-    return check_launch("langfeat_split_bwd_kernel");
+        return launch_split_bwd<float>(d_txt, t32, d_child, d_parent, d_sum, s32, child, parent, heads, drop, ld_drop, B, N, d, slope, d_pre, (hipStream_t)stream);
+    return launch_split_bwd<uint16_t>(d_txt, t32, d_child, d_parent, d_sum, s32, child, parent, heads, drop, ld_drop, B, N, d, slope, d_pre, (hipStream_t)stream);
 }
 
 int vlg_langfeat_marginal(const float* grad_attach, const int64_t* heads, const int64_t* lengths, int B, int N, int use_marginal,
@@ -356,9 +359,8 @@ int vlg_langfeat_marginal(const float* grad_attach, const int64_t* heads, const 
     if (B == 0) return 0;
     if (!lengths || !txt_marginal || !txt_mask || (use_marginal && (!grad_attach || !heads)))
         return set_error(VLG_ERR_ARG, "langfeat_marginal: null buffer");
-    hipLaunchKernelGGL(langfeat_marginal_kernel, dim3((B * N + 255) / 256), dim3(256), 0, (hipStream_t)stream, grad_attach, heads, lengths,
-                       B, N, use_marginal, txt_marginal, txt_mask);
-    return check_launch("langfeat_marginal_kernel");
+    return launch("langfeat_marginal_kernel", langfeat_marginal_kernel, dim3((B * N + 255) / 256), dim3(256), 0, (hipStream_t)stream, grad_attach, heads,
+                  lengths, B, N, use_marginal, txt_marginal, txt_mask);
 }
 
 int vlg_langfeat_arc_out(const float* tri, const void* aff, int B, int N, int d, int act_dtype, void* txt, void* stream) {
@@ -370,10 +372,11 @@ int vlg_langfeat_arc_out(const float* tri, const void* aff, int B, int N, int d,
     const size_t threads = (size_t)B * N * (d / 8);
     const dim3 grid((unsigned)((threads + 255) / 256));
     if (act_dtype == VLG_F32)
-        hipLaunchKernelGGL(langfeat_arc_out_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, tri, (const float*)aff, B, N, d, (float*)txt);
+        return launch("langfeat_arc_out_kernel", langfeat_arc_out_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, tri, (const float*)aff, B, N, d,
+                      (float*)txt);
     else
-        hipLaunchKernelGGL(langfeat_arc_out_kernel<uint16_t>, grid, dim3(256), 0, (hipStream_t)stream, tri, (const uint16_t*)aff, B, N, d, (uint16_t*)txt);
-    return check_launch("langfeat_arc_out_kernel");
+        return launch("langfeat_arc_out_kernel", langfeat_arc_out_kernel<uint16_t>, grid, dim3(256), 0, (hipStream_t)stream, tri, (const uint16_t*)aff, B, N, d,
+                      (uint16_t*)txt);
 }
 
 int vlg_langfeat_rowscale(const void* pre, int ld_in, const float* drop, int B, int N, int d, int ld_drop, int act_dtype, void* out, int ld_out, int width,
@@ -388,12 +391,11 @@ int vlg_langfeat_rowscale(const void* pre, int ld_in, const float* drop, int B, 
     const size_t threads = (size_t)B * N * (width / 8);
     const dim3 grid((unsigned)((threads + 255) / 256));
     if (act_dtype == VLG_F32)
-        hipLaunchKernelGGL(langfeat_rowscale_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)pre, ld_in, drop, B, N, d, ld_drop, (float*)out,
-                           ld_out, width);
+        return launch("langfeat_rowscale_kernel", langfeat_rowscale_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)pre, ld_in, drop, B,
+                      N, d, ld_drop, (float*)out, ld_out, width);
     else
-        hipLaunchKernelGGL(langfeat_rowscale_kernel<uint16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)pre, ld_in, drop, B, N, d, ld_drop,
-                           (uint16_t*)out, ld_out, width);
-    return check_launch("langfeat_rowscale_kernel");
+        return launch("langfeat_rowscale_kernel", langfeat_rowscale_kernel<uint16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)pre, ld_in,
+                      drop, B, N, d, ld_drop, (uint16_t*)out, ld_out, width);
 }
 
 }  // extern "C"

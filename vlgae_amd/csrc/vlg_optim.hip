@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "vlg_common.h"
+#include "vlg_launch.h"
 
 namespace vlg {
 
@@ -351,15 +352,15 @@ int vlg_adam_clip_step(const VlgOptTensor* table, const long long* numel, const 
             L.chunk_start[L.count] = chunks;
             if (pass == 0) {
                 const int grid = chunks < kOptNormGrid ? chunks : kOptNormGrid;
-                hipLaunchKernelGGL(opt_sqsum_kernel, dim3(grid), dim3(kOptThreads), 0, (hipStream_t)stream, table, L, C, first == 0 ? 1 : 0, st, sc,
-                                   slots + slot0);
-                if (int rc = check_launch("opt_sqsum_kernel")) return rc;
+                if (int rc = launch("opt_sqsum_kernel", opt_sqsum_kernel, dim3(grid), dim3(kOptThreads), 0, (hipStream_t)stream, table, L, C,
+                                    first == 0 ? 1 : 0, st, sc, slots + slot0))
+                    return rc;
                 slot0 += grid;
             } else {
                 const int grid = chunks < kOptGrid ? chunks : kOptGrid;
-                hipLaunchKernelGGL(opt_update_kernel, dim3(grid), dim3(kOptThreads), 0, (hipStream_t)stream, table, L, C, first == 0 ? 1 : 0, st,
-                                   (const OptScalars*)sc, (const double*)slots, (int)n_slots);
-                if (int rc = check_launch("opt_update_kernel")) return rc;
+                if (int rc = launch("opt_update_kernel", opt_update_kernel, dim3(grid), dim3(kOptThreads), 0, (hipStream_t)stream, table, L, C,
+                                    first == 0 ? 1 : 0, st, (const OptScalars*)sc, (const double*)slots, (int)n_slots))
+                    return rc;
             }
         }
     }

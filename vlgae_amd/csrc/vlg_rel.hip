@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "vlg_common.h"
+#include "vlg_launch.h"
 #include "vlg_dp_core.h"   // F32In / BF16In
 
 namespace vlg {
@@ -143,10 +144,9 @@ int vlg_box_rel_pairwise(const void* y, const float* bias, int B, int R, int H, 
     if (!y || !out) return set_error(VLG_ERR_ARG, "box_rel_pairwise: null buffer");
     hipStream_t s = (hipStream_t)stream;
     if (dtype == VLG_F32)
-        hipLaunchKernelGGL(box_rel_fwd_kernel<F32In>, dim3(R, B), dim3(256), 0, s, (const float*)y, bias, R, H, slope, (float*)out);
+        return launch("box_rel_fwd_kernel", box_rel_fwd_kernel<F32In>, dim3(R, B), dim3(256), 0, s, (const float*)y, bias, R, H, slope, (float*)out);
     else
-        hipLaunchKernelGGL(box_rel_fwd_kernel<BF16In>, dim3(R, B), dim3(256), 0, s, (const uint16_t*)y, bias, R, H, slope, (uint16_t*)out);
-    return check_launch("box_rel_fwd_kernel");
+        return launch("box_rel_fwd_kernel", box_rel_fwd_kernel<BF16In>, dim3(R, B), dim3(256), 0, s, (const uint16_t*)y, bias, R, H, slope, (uint16_t*)out);
 }
 
 size_t vlg_box_rel_pairwise_backward_workspace(int B, int R, int H) {
@@ -164,16 +164,13 @@ int vlg_box_rel_pairwise_backward(const void* y, const float* bias, const void* 
                          vlg_box_rel_pairwise_backward_workspace(B, R, H));
     hipStream_t s = (hipStream_t)stream;
     float* part = grad_bias ? (float*)ws : nullptr;
-    if (dtype == VLG_F32)
-        hipLaunchKernelGGL(box_rel_bwd_kernel<F32In>, dim3(R, B), dim3(256), 0, s, (const float*)y, bias, (const float*)grad_out, R, H,
-                           slope, grad_y, part);
-    else
-        hipLaunchKernelGGL(box_rel_bwd_kernel<BF16In>, dim3(R, B), dim3(256), 0, s, (const uint16_t*)y, bias,
-                           (const uint16_t*)grad_out, R, H, slope, grad_y, part);
-    if (int rc = check_launch("box_rel_bwd_kernel")) return rc;
+    if (int rc = dtype == VLG_F32 ? launch("box_rel_bwd_kernel", box_rel_bwd_kernel<F32In>, dim3(R, B), dim3(256), 0, s, (const float*)y, bias,
+                                           (const float*)grad_out, R, H, slope, grad_y, part)
+                                  : launch("box_rel_bwd_kernel", box_rel_bwd_kernel<BF16In>, dim3(R, B), dim3(256), 0, s, (const uint16_t*)y, bias,
+                                           (const uint16_t*)grad_out, R, H, slope, grad_y, part))
+        return rc;
     if (grad_bias) {
-        hipLaunchKernelGGL(colsum_kernel, dim3((H + 63) / 64), dim3(1024), 0, s, part, B * R, H, grad_bias);
-        return check_launch("colsum_kernel");
+        return launch("colsum_kernel", colsum_kernel, dim3((H + 63) / 64), dim3(1024), 0, s, part, B * R, H, grad_bias);
     }
     return 0;
 }

@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include "vlg_common.h"
+#include "vlg_launch.h"
 
 namespace vlg {
 
@@ -245,12 +246,11 @@ int vlg_dmv1o_gold_rules(const int64_t* arc, int ld_arc, const int64_t* lengths,
     if (!arc || !lengths || !dec_rule || !attach_rule || !root_rule) return set_error(VLG_ERR_ARG, "dmv1o_gold_rules: null buffer");
     hipStream_t s = (hipStream_t)stream;
     if (out_dtype == VLG_F32)
-        hipLaunchKernelGGL(gold_rules_kernel<float>, dim3(B), dim3(kGoldThreads), 0, s, arc, ld_arc, lengths, L, (float*)dec_rule,
-                           (float*)attach_rule, (float*)root_rule);
+        return launch("gold_rules_kernel", gold_rules_kernel<float>, dim3(B), dim3(kGoldThreads), 0, s, arc, ld_arc, lengths, L, (float*)dec_rule,
+                      (float*)attach_rule, (float*)root_rule);
     else
-        hipLaunchKernelGGL(gold_rules_kernel<double>, dim3(B), dim3(kGoldThreads), 0, s, arc, ld_arc, lengths, L, (double*)dec_rule,
-                           (double*)attach_rule, (double*)root_rule);
-    return check_launch("gold_rules_kernel");
+        return launch("gold_rules_kernel", gold_rules_kernel<double>, dim3(B), dim3(kGoldThreads), 0, s, arc, ld_arc, lengths, L, (double*)dec_rule,
+                      (double*)attach_rule, (double*)root_rule);
 }
 
 int vlg_dmv1o_gold_score(const void* merged_dec, const void* merged_attach, const int64_t* arc, int ld_arc, const int64_t* lengths, int B, int N,
@@ -263,12 +263,11 @@ int vlg_dmv1o_gold_score(const void* merged_dec, const void* merged_attach, cons
     if (!merged_dec || !merged_attach || !arc || !lengths || !score) return set_error(VLG_ERR_ARG, "dmv1o_gold_score: null buffer");
     hipStream_t s = (hipStream_t)stream;
     if (in_dtype == VLG_F32)
-        hipLaunchKernelGGL(gold_score_kernel<F32Load>, dim3(B), dim3(kGoldThreads), 0, s, (const float*)merged_dec, (const float*)merged_attach,
-                           arc, ld_arc, lengths, N, score);
+        return launch("gold_score_kernel", gold_score_kernel<F32Load>, dim3(B), dim3(kGoldThreads), 0, s, (const float*)merged_dec, (const float*)merged_attach,
+                      arc, ld_arc, lengths, N, score);
     else
-        hipLaunchKernelGGL(gold_score_kernel<BF16Load>, dim3(B), dim3(kGoldThreads), 0, s, (const uint16_t*)merged_dec,
-                           (const uint16_t*)merged_attach, arc, ld_arc, lengths, N, score);
-    return check_launch("gold_score_kernel");
+        return launch("gold_score_kernel", gold_score_kernel<BF16Load>, dim3(B), dim3(kGoldThreads), 0, s, (const uint16_t*)merged_dec,
+                      (const uint16_t*)merged_attach, arc, ld_arc, lengths, N, score);
 }
 
 int vlg_dmv1o_gold_score_backward(const int64_t* arc, int ld_arc, const int64_t* lengths, int B, int N, const float* g, int g_stride,
@@ -282,12 +281,11 @@ int vlg_dmv1o_gold_score_backward(const int64_t* arc, int ld_arc, const int64_t*
     if (!arc || !lengths || !g || !grad_dec || !grad_attach) return set_error(VLG_ERR_ARG, "dmv1o_gold_score_backward: null buffer");
     hipStream_t s = (hipStream_t)stream;
     if (out_dtype == VLG_F32)
-        hipLaunchKernelGGL(gold_score_grad_kernel<float>, dim3(B), dim3(kGoldThreads), 0, s, arc, ld_arc, lengths, N, g, g_stride,
-                           (float*)grad_dec, (float*)grad_attach);
+        return launch("gold_score_grad_kernel", gold_score_grad_kernel<float>, dim3(B), dim3(kGoldThreads), 0, s, arc, ld_arc, lengths, N, g, g_stride,
+                      (float*)grad_dec, (float*)grad_attach);
     else
-        hipLaunchKernelGGL(gold_score_grad_kernel<__bf16>, dim3(B), dim3(kGoldThreads), 0, s, arc, ld_arc, lengths, N, g, g_stride,
-                           (__bf16*)grad_dec, (__bf16*)grad_attach);
-    return check_launch("gold_score_grad_kernel");
+        return launch("gold_score_grad_kernel", gold_score_grad_kernel<__bf16>, dim3(B), dim3(kGoldThreads), 0, s, arc, ld_arc, lengths, N, g, g_stride,
+                      (__bf16*)grad_dec, (__bf16*)grad_attach);
 }
 
 }  // extern "C"

@@ -124,12 +124,9 @@ struct SampleArgs {
 
 template <int MODE, typename In>
 static int launch_sample(const SampleArgs& a) {
-    auto k = deptree_sample_kernel<MODE, In>;
     const size_t lds = a.lds_charts + kSampleStackBytes;
-    if (int rc = prep(k, lds)) return rc;
-    hipLaunchKernelGGL(k, dim3(a.B, a.Y), dim3(kThreads), lds, a.s, (const typename In::T*)a.arc, a.lengths, a.N, a.S,
-                       (a.S + a.Y - 1) / a.Y, a.rng, a.site, a.u, (long long*)a.heads, a.logp, a.logZ, (char*)a.ws, a.ws_stride, a.lds_charts);
-    return check_launch("deptree_sample_kernel");
+    return launch("deptree_sample_kernel", deptree_sample_kernel<MODE, In>, dim3(a.B, a.Y), dim3(kThreads), lds, a.s, (const typename In::T*)a.arc, a.lengths,
+                  a.N, a.S, (a.S + a.Y - 1) / a.Y, a.rng, a.site, a.u, (long long*)a.heads, a.logp, a.logZ, (char*)a.ws, a.ws_stride, a.lds_charts);
 }
 
 template <typename In>

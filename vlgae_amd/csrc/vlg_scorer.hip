@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include "vlg_common.h"
+#include "vlg_launch.h"
 #include "vlg_dp_core.h"
 
 namespace vlg {
@@ -319,15 +320,6 @@ int check_shape(const char* what, int B, int L, int T, int r, bool bwd, size_t* 
     return 0;
 }
 
-template <typename K>
-int prep_lds(K kernel, size_t lds) {
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return set_error((int)e, "hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(e));
-    }
-    return 0;
-}
-
 }  // namespace
 
 }  // namespace vlg
@@ -348,27 +340,14 @@ int vlg_ndmv_potentials(const void* x1, int ld_x1, const void* x2, int ld_x2, co
     if (B == 0) return 0;
     if (!x1 || !x2 || !y1 || !y2 || !root_rule || !token || !merged_dec || !merged_attach) return set_error(VLG_ERR_ARG, "ndmv_potentials: null buffer");
     hipStream_t s = (hipStream_t)stream;
-#define VLG_GO_R(IN, OUT, RR)                                                                                                       \
-    {                                                                                                                               \
-        auto k = scorer_fwd_kernel<IN, OUT, RR>;                                                                                    \
-        if (int rc = prep_lds(k, lds)) return rc;                                                                                   \
-        hipLaunchKernelGGL(k, dim3(B), dim3(kScThreads), lds, s, (const IN::T*)x1, (const IN::T*)x2, (const IN::T*)y1, (const IN::T*)y2, \
-                           root_rule, token, head_mask, L, T, r, ld, mask_fill, (OUT*)merged_dec, (OUT*)merged_attach);            \
-    }
-#define VLG_GO(IN, OUT)                                  \
-    {                                                    \
-        if (r == 16) VLG_GO_R(IN, OUT, 16)               \
-        else if (r == 8) VLG_GO_R(IN, OUT, 8)            \
-        else if (r == 32) VLG_GO_R(IN, OUT, 32)          \
-        else VLG_GO_R(IN, OUT, 0)                        \
-    }
-    if (in_dtype == VLG_F32 && out_dtype == VLG_F32) VLG_GO(F32In, float)
-    else if (in_dtype == VLG_F32) VLG_GO(F32In, __bf16)
-    else if (out_dtype == VLG_F32) VLG_GO(BF16In, float)
-    else VLG_GO(BF16In, __bf16)
+#define VLG_GO_R(IN, OUT, RR)                                                                                                           \
+    launch("scorer_fwd_kernel", scorer_fwd_kernel<IN, OUT, RR>, dim3(B), dim3(kScThreads), lds, s, (const IN::T*)x1, (const IN::T*)x2,  \
+           (const IN::T*)y1, (const IN::T*)y2, root_rule, token, head_mask, L, T, r, ld, mask_fill, (OUT*)merged_dec, (OUT*)merged_attach)
+#define VLG_GO(IN, OUT) (r == 16 ? VLG_GO_R(IN, OUT, 16) : r == 8 ? VLG_GO_R(IN, OUT, 8) : r == 32 ? VLG_GO_R(IN, OUT, 32) : VLG_GO_R(IN, OUT, 0))
+    if (in_dtype == VLG_F32) return out_dtype == VLG_F32 ? VLG_GO(F32In, float) : VLG_GO(F32In, __bf16);
+    return out_dtype == VLG_F32 ? VLG_GO(BF16In, float) : VLG_GO(BF16In, __bf16);
 #undef VLG_GO
 #undef VLG_GO_R
-    return check_launch("scorer_fwd_kernel");
 }
 
 size_t vlg_ndmv_potentials_backward_workspace(int B, int L, int T, int r) {
@@ -402,34 +381,21 @@ int vlg_ndmv_potentials_backward(const void* x1, int ld_x1, const void* x2, int 
     const size_t need = vlg_ndmv_potentials_backward_workspace(B, L, T, r);
     if (!ws || ws_bytes < need) return set_error(VLG_ERR_WORKSPACE, "ndmv_potentials_backward: workspace %zu bytes < %zu", ws_bytes, need);
     const ScLd ld{ld_x1, ld_x2, ld_y1, ld_y2};
-#define VLG_GO_R(IN, RR, G)                                                                                                         \
-    {                                                                                                                               \
-        auto k = scorer_bwd_kernel<IN, RR, G>;                                                                                      \
-        if (int rc = prep_lds(k, lds)) return rc;                                                                                   \
-        hipLaunchKernelGGL(k, dim3(B), dim3(kScThreads), lds, s, (const IN::T*)x1, (const IN::T*)x2, (const IN::T*)y1, (const IN::T*)y2, \
-                           token, head_mask, g_merged_dec, g_merged_attach, L, T, r, ld, (G*)d_x1, ld_dx1, (G*)d_y1, ld_dy1, (float*)ws); \
-    }
-#define VLG_GO(IN, G)                                  \
-    {                                                  \
-        if (r == 16) VLG_GO_R(IN, 16, G)               \
-        else if (r == 8) VLG_GO_R(IN, 8, G)            \
-        else if (r == 32) VLG_GO_R(IN, 32, G)          \
-        else VLG_GO_R(IN, 0, G)                        \
-    }
-    if (in_dtype == VLG_F32 && grad_dtype == VLG_F32) VLG_GO(F32In, float)
-    else if (in_dtype == VLG_F32) VLG_GO(F32In, uint16_t)
-    else if (grad_dtype == VLG_F32) VLG_GO(BF16In, float)
-    else VLG_GO(BF16In, uint16_t)
+#define VLG_GO_R(IN, RR, G)                                                                                                                 \
+    launch("scorer_bwd_kernel", scorer_bwd_kernel<IN, RR, G>, dim3(B), dim3(kScThreads), lds, s, (const IN::T*)x1, (const IN::T*)x2, (const IN::T*)y1, \
+           (const IN::T*)y2, token, head_mask, g_merged_dec, g_merged_attach, L, T, r, ld, (G*)d_x1, ld_dx1, (G*)d_y1, ld_dy1, (float*)ws)
+#define VLG_GO(IN, G) (r == 16 ? VLG_GO_R(IN, 16, G) : r == 8 ? VLG_GO_R(IN, 8, G) : r == 32 ? VLG_GO_R(IN, 32, G) : VLG_GO_R(IN, 0, G))
+    if (int rc = in_dtype == VLG_F32 ? (grad_dtype == VLG_F32 ? VLG_GO(F32In, float) : VLG_GO(F32In, uint16_t))
+                                     : (grad_dtype == VLG_F32 ? VLG_GO(BF16In, float) : VLG_GO(BF16In, uint16_t)))
+        return rc;
 #undef VLG_GO
 #undef VLG_GO_R
-    if (int rc = check_launch("scorer_bwd_kernel")) return rc;
     if (grad_dtype == VLG_F32)
-        hipLaunchKernelGGL(scorer_reduce_kernel<float>, dim3((n + 63) / 64), dim3(256), 0, s, (const float*)ws, B, n, (float*)d_x2, n_x2, (float*)d_y2,
-                           n_y2, d_root_rule);
+        return launch("scorer_reduce_kernel", scorer_reduce_kernel<float>, dim3((n + 63) / 64), dim3(256), 0, s, (const float*)ws, B, n, (float*)d_x2, n_x2,
+                      (float*)d_y2, n_y2, d_root_rule);
     else
-        hipLaunchKernelGGL(scorer_reduce_kernel<uint16_t>, dim3((n + 63) / 64), dim3(256), 0, s, (const float*)ws, B, n, (uint16_t*)d_x2, n_x2,
-                           (uint16_t*)d_y2, n_y2, d_root_rule);
-    return check_launch("scorer_reduce_kernel");
+        return launch("scorer_reduce_kernel", scorer_reduce_kernel<uint16_t>, dim3((n + 63) / 64), dim3(256), 0, s, (const float*)ws, B, n, (uint16_t*)d_x2,
+                      n_x2, (uint16_t*)d_y2, n_y2, d_root_rule);
 }
 
 }  // extern "C"
