@@ -114,6 +114,84 @@ def test_workspace_sizing(lib):
     assert lib.vlg_workspace_bytes(99, 4, 41, 0) == 0 and lib.vlg_workspace_bytes(0, 0, 41, 0) == 0
 
 
+def test_workspace_query_and_launchers_agree_at_every_width(lib):
+    """Every DP entry point that takes a workspace, every N in 2..255, both semirings: one byte less than vlg_workspace_bytes says
+    (with the op and semiring include/vlgae_amd.h documents for the entry) is refused with VLG_ERR_WORKSPACE before any launch, and
+    the message names the queried size -- the query and the launcher size the same layout.  (Never a sufficient size: that would
+    launch.  Where the query says 0 the charts live in LDS and there is nothing to refuse.)"""
+    from vlgae_amd import _C
+    one, B, S = ctypes.c_void_p(16), 3, 64
+    IN, IO, DIN, DIO = _C.OP_DMV1O_INSIDE, _C.OP_DMV1O_INSIDE_OUTSIDE, _C.OP_DEPTREE_INSIDE, _C.OP_DEPTREE_INSIDE_OUTSIDE
+    q = lib.vlg_workspace_bytes
+
+    def rules(N, sr, grads, heads, ws):
+        g = one if grads else None
+        return lib.vlg_dmv1o_rules(one, one, one, 0, one, None, one, B, N - 1, 5, 0, sr, -1e20, None, one, g, g, g, one if heads else None, one, ws, None)
+    # name -> (semirings, need(N, sr), call(N, sr, ws_bytes))
+    entries = {
+        "dmv1o_inside": ((0, 1), lambda N, sr: q(IN, B, N, sr), lambda N, sr, ws: lib.vlg_dmv1o_inside(one, one, one, B, N, 0, sr, one, one, ws, None)),
+        "dmv1o_inside_outside": ((0, 1), lambda N, sr: q(IO, B, N, sr),
+                                 lambda N, sr, ws: lib.vlg_dmv1o_inside_outside(one, one, one, B, N, 0, sr, None, one, one, one, one, ws, None)),
+        "dmv1o_decode": ((1,), lambda N, sr: q(IO, B, N, 1), lambda N, sr, ws: lib.vlg_dmv1o_decode(one, one, one, B, N, 0, one, one, one, ws, None)),
+        "dmv1o_viterbi": ((1,), lambda N, sr: q(IO, B, N, 1), lambda N, sr, ws: lib.vlg_dmv1o_viterbi(one, one, one, B, N, 0, None, one, one, one, one, one, ws, None)),
+        "dmv1o_rules inside": ((0, 1), lambda N, sr: q(IN, B, N, sr), lambda N, sr, ws: rules(N, sr, False, False, ws)),
+        "dmv1o_rules gradients": ((0, 1), lambda N, sr: q(IO, B, N, sr), lambda N, sr, ws: rules(N, sr, True, False, ws)),
+        "dmv1o_rules heads": ((1,), lambda N, sr: q(IO, B, N, 1), lambda N, sr, ws: rules(N, 1, False, True, ws)),
+        "deptree_inside": ((0, 1), lambda N, sr: q(DIN, B, N, sr), lambda N, sr, ws: lib.vlg_deptree_inside(one, one, B, N, 0, sr, one, one, ws, None)),
+        "deptree_inside_outside": ((0, 1), lambda N, sr: q(DIO, B, N, sr),
+                                   lambda N, sr, ws: lib.vlg_deptree_inside_outside(one, one, B, N, 0, sr, None, one, one, one, ws, None)),
+        "deptree_decode": ((1,), lambda N, sr: q(DIO, B, N, 1), lambda N, sr, ws: lib.vlg_deptree_decode(one, one, B, N, 0, one, one, one, ws, None)),
+        "deptree_mbr_decode": ((1,), lambda N, sr: q(DIO, B, N, 1), lambda N, sr, ws: lib.vlg_deptree_mbr_decode(one, one, B, N, one, one, one, ws, None)),
+        "deptree_sample": ((0,), lambda N, sr: q(DIN, B * lib.vlg_deptree_sample_blocks(B, N, S), N, 0),
+                           lambda N, sr, ws: lib.vlg_deptree_sample(one, one, B, N, 0, S, one, 0, None, one, one, one, one, ws, None)),
+    }
+    for name, (semirings, need_of, call) in entries.items():
+        spilled = 0
+        for sr in semirings:
+            for N in range(2, 256):
+                need = need_of(N, sr)
+                if need > 0:
+                    spilled += 1
+                    assert call(N, sr, need - 1) == 0x1004, (name, N, sr, need, lib.vlg_last_error())
+                    assert str(need).encode() in lib.vlg_last_error(), (name, N, sr, need, lib.vlg_last_error())
+        assert spilled > 0 and need_of(2, semirings[0]) == 0 and need_of(255, semirings[0]) > 0, name
+
+
+def test_pair_kernel_support_range(lib):
+    """vlg_dmv1o_marginals_viterbi_supported(N) is 1 exactly where both passes keep every chart in LDS (both inside-outside queries
+    return 0) and twice the larger of the two LDS sizes fits the 160 KiB of a CU.  The LDS sizes restate the mode-0 carve from the
+    per-cell tables the placement tests pin (test_dmv_placements_gpu.py: LOG_IO[3] and MAX_WALK[2] hold every chart) plus the staging
+    behind them: dec [N][8] floats in both, the walk's stack of 2 N + 4 ints and its STOP counts [N][4] floats in the Max walk."""
+    from vlgae_amd import _C
+
+    def align16(x):
+        return (x + 15) & ~15
+
+    def charts(N, bytes_per_cell):
+        return sum(align16(N * ((N + 1) | 1) * b) for b in bytes_per_cell)
+
+    def fits(N):
+        lds_log = charts(N, [8, 8, 4, 4, 8, 8]) + align16(32 * N)
+        lds_max = charts(N, [8, 8, 1, 2, 8]) + align16((2 * N + 4) * 4) + align16(32 * N) + align16(16 * N)
+        return (lib.vlg_workspace_bytes(_C.OP_DMV1O_INSIDE_OUTSIDE, 1, N, 0) == 0 and lib.vlg_workspace_bytes(_C.OP_DMV1O_INSIDE_OUTSIDE, 1, N, 1) == 0
+                and 2 * max(lds_log, lds_max) <= 160 * 1024)
+    supported = [N for N in range(-1, 300) if lib.vlg_dmv1o_marginals_viterbi_supported(N)]
+    assert supported == [N for N in range(2, 256) if fits(N)]
+    assert supported == list(range(2, 45))   # the largest supported width: N = 44
+
+
+def test_dp_plan_has_one_spelling():
+    # dp_plan (vlg_dp_core.h) is the only caller of pick_mode and the only place that picks the short-sentence image; the launchers and
+    # the size query build no layout of their own
+    csrc = os.path.join(ROOT, "vlgae_amd", "csrc")
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc))}
+    assert [f for f in text if "pick_mode" in text[f]] == ["vlg_dp_core.h"]
+    for f in ("vlg_dp.hip", "vlg_sample.hip", "vlg_dp_pair.hip"):
+        assert "DmvLayout(" not in text[f] and "DepLayout(" not in text[f], f
+        assert not re.search(r"D(mv|ep)Layout\s+\w+\s*[({]", text[f]), f   # nor a named one
+    assert len([f for f in text if "<= kShortN ? kModeShort" in text[f]]) == 1
+
+
 def test_attn_and_grounding_entry_points_validate_on_the_host(lib):
     """Same contract for the later entry points: shape / dtype / null / workspace errors before any HIP call."""
     P = ctypes.c_void_p

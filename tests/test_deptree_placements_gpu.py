@@ -143,7 +143,7 @@ INSIDE = {0: [], 1: [4, 4]}                                               # C, I
     ("inside", SR_MAX, INSIDE, [(142, 0), (143, 1), (255, 1)]),
 ], ids=["log_inside_outside", "max_walk", "log_inside", "max_inside"])
 def test_placement_boundaries_are_where_the_cases_assume(op, sr, table, edges):
-    """vlg_workspace_bytes is the launcher's own pick_mode + DepLayout: the per-sentence workspace names the placement mode.
+    """vlg_workspace_bytes reads the launchers' own plan (dp_plan<DepLayout>): the per-sentence workspace names the placement mode.
     If a layout change moves a boundary, this fails instead of the cases below quietly running in another mode."""
     from vlgae_amd import _C
     code = _C.OP_DEPTREE_INSIDE_OUTSIDE if op == "io" else _C.OP_DEPTREE_INSIDE

@@ -141,47 +141,30 @@ __global__ __launch_bounds__(256) void scale_counts_kernel(const float* __restri
     ((sr) == VLG_SR_LOG ? ((in) == VLG_F32 ? VLG_DP_INST_NAME(F, 0, 0) : VLG_DP_INST_NAME(F, 0, 1)) \
                         : ((in) == VLG_F32 ? VLG_DP_INST_NAME(F, 1, 0) : VLG_DP_INST_NAME(F, 1, 1)))
 
-template <bool BWD>
-static int run_dmv(const void* dec, const void* attach, const int64_t* lengths, int B, int N, int in_dtype,
+static int run_dmv(bool bwd, const void* dec, const void* attach, const int64_t* lengths, int B, int N, int in_dtype,
                    int semiring, const float* glogZ, float* logZ, float* gdec, float* gatt, int64_t* heads, void* ws,
                    size_t ws_bytes, void* stream) {
-    if (B < 0 || N < 2) return set_error(VLG_ERR_SHAPE, "dmv1o: need B >= 0 and N >= 2 (got B=%d N=%d)", B, N);
-    if (N > 255) return set_error(VLG_ERR_SHAPE, "dmv1o: N=%d exceeds the supported maximum of 255", N);
-    if (in_dtype != VLG_F32 && in_dtype != VLG_BF16) return set_error(VLG_ERR_DTYPE, "dmv1o: in_dtype %d", in_dtype);
-    if (semiring != VLG_SR_LOG && semiring != VLG_SR_MAX) return set_error(VLG_ERR_ARG, "dmv1o: semiring %d", semiring);
-    if (!dec || !attach || !lengths || !logZ || (BWD && !heads && !gatt))   // gdec may be null: attach counts only
+    if (int e = check_dp_args("dmv1o", B, N, in_dtype, semiring)) return e;
+    if (!dec || !attach || !lengths || !logZ || (bwd && !heads && !gatt))   // gdec may be null: attach counts only
         if (B > 0) return set_error(VLG_ERR_ARG, "dmv1o: null buffer");
     if (B == 0) return 0;
-    const bool walk = BWD && semiring == VLG_SR_MAX;   // the Max semiring's outside pass is the back-pointer walk: lean layout (the kernel derives the same flag)
-    const int mode = pick_mode<DmvLayout>(N, BWD, semiring == VLG_SR_MAX, kLdsBudget, walk);
-    const DmvLayout L(N, BWD, semiring == VLG_SR_MAX, mode, walk);
-    const size_t ws_stride = L.ws_bytes, lds = L.lds_bytes;
-    if (ws_stride * (size_t)B > ws_bytes || (ws_stride && !ws))
-        return set_error(VLG_ERR_WORKSPACE, "dmv1o: N=%d needs a %zu-byte workspace (got %zu); see vlg_workspace_bytes",
-                         N, ws_stride * (size_t)B, ws_bytes);
-    const DmvArgs a{dec, attach, lengths, B, N, glogZ, logZ, gdec, gatt, heads, ws, ws_stride, lds, (hipStream_t)stream};
-    return VLG_DP_PICK(0, semiring, in_dtype)(BWD, mode == 0 && N <= kShortN ? kModeShort : mode, a);   // short sentences: the smaller code image
+    const DpPlan p = dp_plan<DmvLayout>(N, bwd, semiring == VLG_SR_MAX);
+    if (int e = check_dp_workspace("dmv1o", N, p, B, ws, ws_bytes)) return e;
+    const DmvArgs a{dec, attach, lengths, B, N, glogZ, logZ, gdec, gatt, heads, ws, p.ws_stride, p.lds_bytes, (hipStream_t)stream};
+    return VLG_DP_PICK(0, semiring, in_dtype)(bwd, p.image, a);
 }
 
-template <bool BWD>
-static int run_dep(const void* arc, const int64_t* lengths, int B, int N, int in_dtype, int semiring,
+static int run_dep(bool bwd, const void* arc, const int64_t* lengths, int B, int N, int in_dtype, int semiring,
                    const float* glogZ, float* logZ, float* garc, int64_t* heads, void* ws, size_t ws_bytes,
                    void* stream) {
-    if (B < 0 || N < 2) return set_error(VLG_ERR_SHAPE, "deptree: need B >= 0 and N >= 2 (got B=%d N=%d)", B, N);
-    if (N > 255) return set_error(VLG_ERR_SHAPE, "deptree: N=%d exceeds the supported maximum of 255", N);
-    if (in_dtype != VLG_F32 && in_dtype != VLG_BF16) return set_error(VLG_ERR_DTYPE, "deptree: in_dtype %d", in_dtype);
-    if (semiring != VLG_SR_LOG && semiring != VLG_SR_MAX) return set_error(VLG_ERR_ARG, "deptree: semiring %d", semiring);
-    if (!arc || !logZ || (BWD && !garc && !heads))
+    if (int e = check_dp_args("deptree", B, N, in_dtype, semiring)) return e;
+    if (!arc || !logZ || (bwd && !garc && !heads))
         if (B > 0) return set_error(VLG_ERR_ARG, "deptree: null buffer");
     if (B == 0) return 0;
-    const int mode = pick_mode<DepLayout>(N, BWD, semiring == VLG_SR_MAX, kLdsBudget);
-    const DepLayout L(N, BWD, semiring == VLG_SR_MAX, mode);
-    const size_t ws_stride = L.ws_bytes, lds = L.lds_bytes;
-    if (ws_stride * (size_t)B > ws_bytes || (ws_stride && !ws))
-        return set_error(VLG_ERR_WORKSPACE, "deptree: N=%d needs a %zu-byte workspace (got %zu)", N,
-                         ws_stride * (size_t)B, ws_bytes);
-    const DepArgs a{arc, lengths, B, N, glogZ, logZ, garc, heads, ws, ws_stride, lds, (hipStream_t)stream};
-    return VLG_DP_PICK(2, semiring, in_dtype)(BWD, mode == 0 && N <= kShortN ? kModeShort : mode, a);
+    const DpPlan p = dp_plan<DepLayout>(N, bwd, semiring == VLG_SR_MAX);
+    if (int e = check_dp_workspace("deptree", N, p, B, ws, ws_bytes)) return e;
+    const DepArgs a{arc, lengths, B, N, glogZ, logZ, garc, heads, ws, p.ws_stride, p.lds_bytes, (hipStream_t)stream};
+    return VLG_DP_PICK(2, semiring, in_dtype)(bwd, p.image, a);
 }
 
 }  // namespace vlg
@@ -202,33 +185,33 @@ extern "C" {
 
 int vlg_dmv1o_inside(const void* dec, const void* attach, const int64_t* lengths, int B, int N, int in_dtype,
                      int semiring, float* logZ, void* ws, size_t ws_bytes, void* stream) {
-    return vlg::run_dmv<false>(dec, attach, lengths, B, N, in_dtype, semiring, nullptr, logZ, nullptr, nullptr, nullptr,
-                               ws, ws_bytes, stream);
+    return vlg::run_dmv(false, dec, attach, lengths, B, N, in_dtype, semiring, nullptr, logZ, nullptr, nullptr, nullptr,
+                        ws, ws_bytes, stream);
 }
 
 int vlg_dmv1o_inside_outside(const void* dec, const void* attach, const int64_t* lengths, int B, int N, int in_dtype,
                              int semiring, const float* grad_logZ, float* logZ, float* grad_dec, float* grad_attach,
                              void* ws, size_t ws_bytes, void* stream) {
-    return vlg::run_dmv<true>(dec, attach, lengths, B, N, in_dtype, semiring, grad_logZ, logZ, grad_dec, grad_attach,
-                              nullptr, ws, ws_bytes, stream);
+    return vlg::run_dmv(true, dec, attach, lengths, B, N, in_dtype, semiring, grad_logZ, logZ, grad_dec, grad_attach,
+                        nullptr, ws, ws_bytes, stream);
 }
 
 int vlg_deptree_inside(const void* arc, const int64_t* lengths, int B, int N, int in_dtype, int semiring, float* logZ,
                        void* ws, size_t ws_bytes, void* stream) {
-    return vlg::run_dep<false>(arc, lengths, B, N, in_dtype, semiring, nullptr, logZ, nullptr, nullptr, ws, ws_bytes, stream);
+    return vlg::run_dep(false, arc, lengths, B, N, in_dtype, semiring, nullptr, logZ, nullptr, nullptr, ws, ws_bytes, stream);
 }
 
 int vlg_deptree_inside_outside(const void* arc, const int64_t* lengths, int B, int N, int in_dtype, int semiring,
                                const float* grad_logZ, float* logZ, float* grad_arc, void* ws, size_t ws_bytes,
                                void* stream) {
-    return vlg::run_dep<true>(arc, lengths, B, N, in_dtype, semiring, grad_logZ, logZ, grad_arc, nullptr, ws, ws_bytes, stream);
+    return vlg::run_dep(true, arc, lengths, B, N, in_dtype, semiring, grad_logZ, logZ, grad_arc, nullptr, ws, ws_bytes, stream);
 }
 
 int vlg_dmv1o_decode(const void* dec, const void* attach, const int64_t* lengths, int B, int N, int in_dtype,
                      float* best_score, int64_t* heads, void* ws, size_t ws_bytes, void* stream) {
     if (B > 0 && !heads) return vlg::set_error(VLG_ERR_ARG, "dmv1o_decode: null heads");
-    return vlg::run_dmv<true>(dec, attach, lengths, B, N, in_dtype, VLG_SR_MAX, nullptr, best_score, nullptr, nullptr,
-                              heads, ws, ws_bytes, stream);
+    return vlg::run_dmv(true, dec, attach, lengths, B, N, in_dtype, VLG_SR_MAX, nullptr, best_score, nullptr, nullptr,
+                        heads, ws, ws_bytes, stream);
 }
 
 int vlg_dmv1o_viterbi(const void* dec, const void* attach, const int64_t* lengths, int B, int N, int in_dtype,
@@ -236,30 +219,27 @@ int vlg_dmv1o_viterbi(const void* dec, const void* attach, const int64_t* length
                       size_t ws_bytes, void* stream) {
     if (B > 0 && !heads && !grad_attach) return vlg::set_error(VLG_ERR_ARG, "dmv1o_viterbi: pass grad_attach and / or heads");
     if (B > 0 && grad_dec && !grad_attach) return vlg::set_error(VLG_ERR_ARG, "dmv1o_viterbi: grad_dec needs grad_attach");
-    return vlg::run_dmv<true>(dec, attach, lengths, B, N, in_dtype, VLG_SR_MAX, grad_best, best_score, grad_dec, grad_attach,
-                              heads, ws, ws_bytes, stream);
+    return vlg::run_dmv(true, dec, attach, lengths, B, N, in_dtype, VLG_SR_MAX, grad_best, best_score, grad_dec, grad_attach,
+                        heads, ws, ws_bytes, stream);
 }
 
 int vlg_deptree_decode(const void* arc, const int64_t* lengths, int B, int N, int in_dtype, float* best_score,
                        int64_t* heads, void* ws, size_t ws_bytes, void* stream) {
     if (B > 0 && !heads) return vlg::set_error(VLG_ERR_ARG, "deptree_decode: null heads");
-    return vlg::run_dep<true>(arc, lengths, B, N, in_dtype, VLG_SR_MAX, nullptr, best_score, nullptr, heads, ws,
-                              ws_bytes, stream);
+    return vlg::run_dep(true, arc, lengths, B, N, in_dtype, VLG_SR_MAX, nullptr, best_score, nullptr, heads, ws,
+                        ws_bytes, stream);
 }
 
 int vlg_deptree_mbr_decode(const float* marginals, const int64_t* lengths, int B, int N, float* best_score, int64_t* heads, void* ws,
                            size_t ws_bytes, void* stream) {
     using namespace vlg;
-    if (B < 0 || N < 2) return set_error(VLG_ERR_SHAPE, "deptree_mbr_decode: need B >= 0 and N >= 2 (got B=%d N=%d)", B, N);
-    if (N > 255) return set_error(VLG_ERR_SHAPE, "deptree_mbr_decode: N=%d exceeds the supported maximum of 255", N);
+    if (int e = check_dp_args("deptree_mbr_decode", B, N, VLG_F32, VLG_SR_MAX)) return e;   // fp32 marginals, Max semiring
     if (B == 0) return 0;
     if (!marginals || !best_score || !heads) return set_error(VLG_ERR_ARG, "deptree_mbr_decode: null buffer");
-    const int mode = pick_mode<DepLayout>(N, true, true, kLdsBudget);
-    const DepLayout L(N, true, true, mode);
-    if (L.ws_bytes * (size_t)B > ws_bytes || (L.ws_bytes && !ws))
-        return set_error(VLG_ERR_WORKSPACE, "deptree_mbr_decode: N=%d needs a %zu-byte workspace (got %zu)", N, L.ws_bytes * (size_t)B, ws_bytes);
-    const DepArgs a{marginals, lengths, B, N, nullptr, best_score, nullptr, heads, ws, L.ws_bytes, L.lds_bytes, (hipStream_t)stream};
-    return VLG_DP_INST_NAME(2, 1, 2)(true, mode == 0 && N <= kShortN ? kModeShort : mode, a);
+    const DpPlan p = dp_plan<DepLayout>(N, true, true);
+    if (int e = check_dp_workspace("deptree_mbr_decode", N, p, B, ws, ws_bytes)) return e;
+    const DepArgs a{marginals, lengths, B, N, nullptr, best_score, nullptr, heads, ws, p.ws_stride, p.lds_bytes, (hipStream_t)stream};
+    return VLG_DP_INST_NAME(2, 1, 2)(true, p.image, a);
 }
 
 int vlg_dmv1o_rules(const void* attach_rule, const void* dec, const void* root_rule, int root_per_sentence,
@@ -268,10 +248,8 @@ int vlg_dmv1o_rules(const void* attach_rule, const void* dec, const void* root_r
                     float* grad_dec, float* grad_root, int64_t* heads, void* ws, size_t ws_bytes, void* stream) {
     using namespace vlg;
     const int N = L + 1;
-    if (B < 0 || L < 1 || T < 1) return set_error(VLG_ERR_SHAPE, "dmv1o_rules: bad shape B=%d L=%d T=%d", B, L, T);
-    if (N > 255) return set_error(VLG_ERR_SHAPE, "dmv1o_rules: L=%d exceeds the supported maximum of 254", L);
-    if (in_dtype != VLG_F32 && in_dtype != VLG_BF16) return set_error(VLG_ERR_DTYPE, "dmv1o_rules: in_dtype %d", in_dtype);
-    if (semiring != VLG_SR_LOG && semiring != VLG_SR_MAX) return set_error(VLG_ERR_ARG, "dmv1o_rules: semiring %d", semiring);
+    if (T < 1) return set_error(VLG_ERR_SHAPE, "dmv1o_rules: need T >= 1 (got T=%d)", T);
+    if (int e = check_dp_args("dmv1o_rules", B, N, in_dtype, semiring)) return e;   // N = L + 1
     if (B == 0) return 0;
     if (!attach_rule || !dec || !root_rule || !token || !lengths || !logZ) return set_error(VLG_ERR_ARG, "dmv1o_rules: null buffer");
     if (heads && semiring != VLG_SR_MAX)
@@ -279,12 +257,8 @@ int vlg_dmv1o_rules(const void* attach_rule, const void* dec, const void* root_r
     const bool bwd = grad_rule || grad_dec || grad_root || heads;
     if (bwd && !heads && !(grad_rule && grad_dec && grad_root))
         return set_error(VLG_ERR_ARG, "dmv1o_rules: pass all three gradient buffers (or only heads)");
-    const bool is_max = semiring == VLG_SR_MAX;
-    const bool walk = bwd && is_max;
-    const int mode = pick_mode<DmvLayout>(N, bwd, is_max, kLdsBudget, walk);
-    const DmvLayout Lay(N, bwd, is_max, mode, walk);
-    if (Lay.ws_bytes * (size_t)B > ws_bytes || (Lay.ws_bytes && !ws))
-        return set_error(VLG_ERR_WORKSPACE, "dmv1o_rules: L=%d needs a %zu-byte workspace (got %zu)", L, Lay.ws_bytes * (size_t)B, ws_bytes);
+    const DpPlan p = dp_plan<DmvLayout>(N, bwd, semiring == VLG_SR_MAX);
+    if (int e = check_dp_workspace("dmv1o_rules", N, p, B, ws, ws_bytes)) return e;
     hipStream_t s = (hipStream_t)stream;
     if (grad_rule) {   // rule-space counts are accumulated with atomics: start from zero
         hipError_t e = hipMemsetAsync(grad_rule, 0, sizeof(float) * (size_t)B * L * T * 4, s);
@@ -293,24 +267,19 @@ int vlg_dmv1o_rules(const void* attach_rule, const void* dec, const void* root_r
         if (e != hipSuccess) return set_error((int)e, "hipMemsetAsync: %s", hipGetErrorString(e));
     }
     RulesArgs a{attach_rule, dec, root_rule, root_per_sentence ? T : 0, token, head_mask, lengths, B, L, T, mask_fill,
-                grad_logZ, logZ, grad_rule, grad_dec, grad_root, heads, ws, Lay.ws_bytes, Lay.lds_bytes, s};
-    return VLG_DP_PICK(1, semiring, in_dtype)(bwd, mode == 0 && N <= kShortN ? kModeShort : mode, a);
+                grad_logZ, logZ, grad_rule, grad_dec, grad_root, heads, ws, p.ws_stride, p.lds_bytes, s};
+    return VLG_DP_PICK(1, semiring, in_dtype)(bwd, p.image, a);
 }
 
 size_t vlg_workspace_bytes(int op, int B, int N, int semiring) {
     if (B <= 0 || N < 2) return 0;
     const bool is_max = semiring == VLG_SR_MAX;
     using namespace vlg;
-    switch (op) {
-        case VLG_OP_DMV1O_INSIDE:
-            return DmvLayout(N, false, is_max, pick_mode<DmvLayout>(N, false, is_max, kLdsBudget)).ws_bytes * B;
-        case VLG_OP_DMV1O_INSIDE_OUTSIDE:   // Log: the replay layout; Max: the walk layout (the one-hot replay is not compiled any more, round 4)
-            if (is_max) return DmvLayout(N, true, true, pick_mode<DmvLayout>(N, true, true, kLdsBudget, true), true).ws_bytes * B;
-            return DmvLayout(N, true, false, pick_mode<DmvLayout>(N, true, false, kLdsBudget)).ws_bytes * B;
-        case VLG_OP_DEPTREE_INSIDE:
-            return DepLayout(N, false, is_max, pick_mode<DepLayout>(N, false, is_max, kLdsBudget)).ws_bytes * B;
-        case VLG_OP_DEPTREE_INSIDE_OUTSIDE:
-            return DepLayout(N, true, is_max, pick_mode<DepLayout>(N, true, is_max, kLdsBudget)).ws_bytes * B;
+    switch (op) {   // what the op's launcher asks for, from the same plan
+        case VLG_OP_DMV1O_INSIDE: return dp_plan<DmvLayout>(N, false, is_max).ws_stride * B;
+        case VLG_OP_DMV1O_INSIDE_OUTSIDE: return dp_plan<DmvLayout>(N, true, is_max).ws_stride * B;
+        case VLG_OP_DEPTREE_INSIDE: return dp_plan<DepLayout>(N, false, is_max).ws_stride * B;
+        case VLG_OP_DEPTREE_INSIDE_OUTSIDE: return dp_plan<DepLayout>(N, true, is_max).ws_stride * B;
         default: return 0;
     }
 }

@@ -1826,4 +1826,23 @@ VLG_HOSTDEV int pick_mode(int N, bool bwd, bool is_max, size_t lds_budget, bool 
     return 3;
 }
 
+// ---- the host's plan of one DP launch: which kernel image runs and where a sentence's charts live.  Every launcher and the size
+// query (vlg_workspace_bytes) take it from dp_plan, so they cannot disagree; the emulator (tests/emu) shares the walk rule.
+// Kernel variant MODE: 0 ... 3 = the placement modes of DmvLayout / DepLayout; kModeShort = placement 0 (everything in LDS) with the
+// short-sentence code image (kSpansShort), launched for N <= kShortN.
+constexpr size_t kLdsBudget = 160 * 1024;   // CDNA4 LDS per CU / per workgroup
+constexpr int kModeShort = 4;
+constexpr int placement_of(int mode) { return mode == kModeShort ? 0 : mode; }
+// the Max semiring's outside pass is the back-pointer walk: lean layout (the kernels derive the same flag; DepLayout derives it itself)
+constexpr bool dp_walk(bool bwd, bool is_max) { return bwd && is_max; }
+struct DpPlan { int image; size_t lds_bytes, ws_stride; };   // the kernel's MODE; dynamic LDS of a workgroup; workspace bytes per sentence
+
+template <typename Layout>
+VLG_HOSTDEV DpPlan dp_plan(int N, bool bwd, bool is_max) {
+    const bool walk = dp_walk(bwd, is_max);
+    const int mode = pick_mode<Layout>(N, bwd, is_max, kLdsBudget, walk);
+    const Layout L(N, bwd, is_max, mode, walk);
+    return DpPlan{mode == 0 && N <= kShortN ? kModeShort : mode, L.lds_bytes, L.ws_bytes};   // short sentences: the smaller code image
+}
+
 }  // namespace vlg

@@ -18,7 +18,6 @@ namespace vlg {
                              //  marginals || Viterbi pair of lang_feat_max_tree went from 101 to 145 us -- so it stays 512.)
 #endif
 constexpr int kThreads = VLG_DP_THREADS;    // lanes per sentence (workgroup size)
-constexpr size_t kLdsBudget = 160 * 1024;   // CDNA4 LDS per CU / per workgroup
 #ifdef VLG_STAMP
 // Diagnostic build (tools/time_dp_widths.py): the DMV1o kernels of the first kStampBlocks sentences copy their per-width stamp table
 // (DevX::wstamp) and each wavefront's HW_ID register to vlg_wstamp_dev; the host reads it with vlg_dp_stamps().
@@ -233,10 +232,7 @@ __device__ __forceinline__ T* region_ptr(const Region& r, char* smem, char* wsb)
     return reinterpret_cast<T*>((r.lds ? smem : wsb) + r.off);
 }
 
-// Kernel variant MODE: 0 ... 3 = the placement modes of DmvLayout / DepLayout; kModeShort = placement 0 (everything in LDS) with the
-// short-sentence code image (vlg_dp_core.h: kSpansShort), launched for N <= kShortN.
-constexpr int kModeShort = 4;
-constexpr int placement_of(int mode) { return mode == kModeShort ? 0 : mode; }
+// the span-count policy of a kernel variant MODE (vlg_dp_core.h: DpPlan::image)
 constexpr int spans_of(int mode) { return mode == kModeShort ? kSpansShort : (mode != 0 ? kSpansLong : kSpansGeneral); }
 
 template <int SR, int MODE, bool BWD>
@@ -502,6 +498,23 @@ static int launch_dep(const DepArgs& a) {
     return launch("deptree_kernel", deptree_kernel<SR, MODE, BWD, In>, dim3(a.B), dim3(kThreads), a.lds, a.s,
                   (const typename In::T*)a.arc, a.lengths, a.N, a.glogZ, a.logZ, a.garc, (long long*)a.heads, (char*)a.ws,
                   a.ws_stride);
+}
+
+// ---- the checks every DP entry point makes before it launches (`who` names it in the message) -------
+inline int check_dp_args(const char* who, int B, int N, int in_dtype, int semiring) {
+    if (B < 0 || N < 2) return set_error(VLG_ERR_SHAPE, "%s: need B >= 0 and N >= 2 (got B=%d N=%d)", who, B, N);
+    if (N > 255) return set_error(VLG_ERR_SHAPE, "%s: N=%d exceeds the supported maximum of 255", who, N);
+    if (in_dtype != VLG_F32 && in_dtype != VLG_BF16) return set_error(VLG_ERR_DTYPE, "%s: in_dtype %d", who, in_dtype);
+    if (semiring != VLG_SR_LOG && semiring != VLG_SR_MAX) return set_error(VLG_ERR_ARG, "%s: semiring %d", who, semiring);
+    return 0;
+}
+
+// `blocks` workgroups, each with its own slice of the workspace
+inline int check_dp_workspace(const char* who, int N, const DpPlan& plan, size_t blocks, const void* ws, size_t ws_bytes) {
+    const size_t need = plan.ws_stride * blocks;
+    if (need > ws_bytes || (need && !ws))
+        return set_error(VLG_ERR_WORKSPACE, "%s: N=%d needs a %zu-byte workspace (got %zu); see vlg_workspace_bytes", who, N, need, ws_bytes);
+    return 0;
 }
 
 }  // namespace vlg

@@ -8,20 +8,19 @@ namespace vlg {
 
 namespace {
 
-// both placements must be the everything-in-LDS one (mode 0) and fit one CU TOGETHER: the two workgroups of a sentence run side by side
-bool pair_ok(int N, size_t* lds) {
-    const DmvLayout Llog(N, true, false, 0, false), Lmax(N, true, true, 0, true);
-    *lds = Llog.lds_bytes > Lmax.lds_bytes ? Llog.lds_bytes : Lmax.lds_bytes;
-    return pick_mode<DmvLayout>(N, true, false, kLdsBudget, false) == 0 && pick_mode<DmvLayout>(N, true, true, kLdsBudget, true) == 0 &&
-           2 * *lds <= kLdsBudget;
+// both plans, Log inside-outside and Max walk, must be the everything-in-LDS placement and fit one CU TOGETHER: the two workgroups of a
+// sentence run side by side.  *p: the shared image (both are placement 0 at the same N) with the larger of the two LDS sizes.
+bool pair_ok(int N, DpPlan* p) {
+    const DpPlan lg = dp_plan<DmvLayout>(N, true, false), mx = dp_plan<DmvLayout>(N, true, true);
+    *p = lg.lds_bytes > mx.lds_bytes ? lg : mx;
+    return placement_of(lg.image) == 0 && placement_of(mx.image) == 0 && 2 * p->lds_bytes <= kLdsBudget;
 }
 
 template <typename In>
-int launch_pair(const void* dec, const void* attach, const int64_t* lengths, int B, int N, size_t lds, float* logZ, float* gdec_log,
+int launch_pair(const void* dec, const void* attach, const int64_t* lengths, int B, int N, const DpPlan& p, float* logZ, float* gdec_log,
                 float* gatt_log, float* best, float* gdec_max, float* gatt_max, int64_t* heads, hipStream_t s) {
-    // N <= kShortN: the short-sentence code image (vlg_dp_core.h: kSpansShort)
-    auto k = N <= kShortN ? dmv1o_pair_kernel<In, kModeShort> : dmv1o_pair_kernel<In, 0>;
-    return launch("dmv1o_pair_kernel", k, dim3(B, 2), dim3(kThreads), lds, s, (const typename In::T*)dec, (const typename In::T*)attach, lengths, N, logZ,
+    auto k = p.image == kModeShort ? dmv1o_pair_kernel<In, kModeShort> : dmv1o_pair_kernel<In, 0>;
+    return launch("dmv1o_pair_kernel", k, dim3(B, 2), dim3(kThreads), p.lds_bytes, s, (const typename In::T*)dec, (const typename In::T*)attach, lengths, N, logZ,
                   gdec_log, gatt_log, best, gdec_max, gatt_max, (long long*)heads);
 }
 
@@ -32,8 +31,8 @@ int launch_pair(const void* dec, const void* attach, const int64_t* lengths, int
 extern "C" {
 
 int vlg_dmv1o_marginals_viterbi_supported(int N) {
-    size_t lds;
-    return N >= 2 && N <= 255 && vlg::pair_ok(N, &lds) ? 1 : 0;
+    vlg::DpPlan p;
+    return N >= 2 && N <= 255 && vlg::pair_ok(N, &p) ? 1 : 0;
 }
 
 int vlg_dmv1o_marginals_viterbi(const void* dec, const void* attach, const int64_t* lengths, int B, int N, int in_dtype, float* logZ,
@@ -42,8 +41,8 @@ int vlg_dmv1o_marginals_viterbi(const void* dec, const void* attach, const int64
     using namespace vlg;
     if (B < 0 || N < 2) return set_error(VLG_ERR_SHAPE, "dmv1o_marginals_viterbi: need B >= 0 and N >= 2 (got B=%d N=%d)", B, N);
     if (in_dtype != VLG_F32 && in_dtype != VLG_BF16) return set_error(VLG_ERR_DTYPE, "dmv1o_marginals_viterbi: in_dtype %d", in_dtype);
-    size_t lds = 0;
-    if (N > 255 || !pair_ok(N, &lds))
+    DpPlan p;
+    if (N > 255 || !pair_ok(N, &p))
         return set_error(VLG_ERR_SHAPE, "dmv1o_marginals_viterbi: N=%d -- the two passes do not share a CU's LDS (see vlg_dmv1o_marginals_viterbi_supported); "
                          "launch vlg_dmv1o_inside_outside and vlg_dmv1o_viterbi on two streams", N);
     if (B == 0) return 0;
@@ -51,8 +50,8 @@ int vlg_dmv1o_marginals_viterbi(const void* dec, const void* attach, const int64
         return set_error(VLG_ERR_ARG, "dmv1o_marginals_viterbi: null buffer");
     if (tree_dec && !tree_attach) return set_error(VLG_ERR_ARG, "dmv1o_marginals_viterbi: tree_dec needs tree_attach");
     hipStream_t s = (hipStream_t)stream;
-    return in_dtype == VLG_F32 ? launch_pair<F32In>(dec, attach, lengths, B, N, lds, logZ, grad_dec, grad_attach, best_score, tree_dec, tree_attach, heads, s)
-                               : launch_pair<BF16In>(dec, attach, lengths, B, N, lds, logZ, grad_dec, grad_attach, best_score, tree_dec, tree_attach, heads, s);
+    return in_dtype == VLG_F32 ? launch_pair<F32In>(dec, attach, lengths, B, N, p, logZ, grad_dec, grad_attach, best_score, tree_dec, tree_attach, heads, s)
+                               : launch_pair<BF16In>(dec, attach, lengths, B, N, p, logZ, grad_dec, grad_attach, best_score, tree_dec, tree_attach, heads, s);
 }
 
 }  // extern "C"

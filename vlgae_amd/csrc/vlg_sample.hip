@@ -137,11 +137,10 @@ static int launch_sample_mode(int mode, const SampleArgs& a) {
 
 // Blocks per sentence: enough that B Y workgroups fill the device once, never more than the samples can feed (a wavefront owns whole
 // samples: ceil(S / 8) blocks have one each).  Every further block repeats the inside pass, so Y = 1 as soon as B alone fills the device.
-static int sample_blocks(int B, int N, int S) {
-    const DepLayout L(N, false, false, pick_mode<DepLayout>(N, false, false, kLdsBudget));
-    size_t per_cu = kLdsBudget / (L.lds_bytes + kSampleStackBytes);
+static int sample_blocks(const DpPlan& p, int B, int S) {
+    size_t per_cu = kLdsBudget / (p.lds_bytes + kSampleStackBytes);
     per_cu = per_cu < 1 ? 1 : per_cu > (size_t)kSampleBlocksPerCU ? (size_t)kSampleBlocksPerCU : per_cu;
-    if (L.ws_bytes) per_cu = 1;   // charts in the workspace: every block needs its own slice of it (0.5 MB at N = 255), and its inside pass is the slow one
+    if (p.ws_stride) per_cu = 1;   // charts in the workspace: every block needs its own slice of it (0.5 MB at N = 255), and its inside pass is the slow one
     const int fill = kSampleCUs * (int)per_cu;
     const int want = B >= fill ? 1 : fill / B, cap = (S + kSampleWaves - 1) / kSampleWaves;
     return want < cap ? want : cap;
@@ -153,32 +152,27 @@ extern "C" {
 
 int vlg_deptree_sample_blocks(int B, int N, int S) {
     if (B < 1 || S < 1 || N < 2 || N > 255) return 1;
-    return vlg::sample_blocks(B, N, S);
+    return vlg::sample_blocks(vlg::dp_plan<vlg::DepLayout>(N, false, false), B, S);
 }
 
 int vlg_deptree_sample(const void* arc, const int64_t* lengths, int B, int N, int in_dtype, int S, const uint64_t* rng, unsigned site,
                        const float* u, int64_t* heads, float* logp, float* logZ, void* ws, size_t ws_bytes, void* stream) {
     using namespace vlg;
-    if (B < 0 || N < 2) return set_error(VLG_ERR_SHAPE, "deptree_sample: need B >= 0 and N >= 2 (got B=%d N=%d)", B, N);
-    if (N > 255) return set_error(VLG_ERR_SHAPE, "deptree_sample: N=%d exceeds the supported maximum of 255", N);
+    if (int e = check_dp_args("deptree_sample", B, N, VLG_F32, VLG_SR_LOG)) return e;   // the shape; the dtype's turn is behind S
     if (S < 1) return set_error(VLG_ERR_SHAPE, "deptree_sample: need S >= 1 samples (got %d)", S);
     if (in_dtype != VLG_F32 && in_dtype != VLG_BF16) return set_error(VLG_ERR_DTYPE, "deptree_sample: in_dtype %d", in_dtype);
     if (B == 0) return 0;
     if ((rng != nullptr) == (u != nullptr))
         return set_error(VLG_ERR_NULL, "deptree_sample: pass exactly one of rng (counter-based draws) and u (explicit uniforms)");
     if (!arc || !heads) return set_error(VLG_ERR_NULL, "deptree_sample: null buffer");
-    const int Y = sample_blocks(B, N, S);
-    const int mode = pick_mode<DepLayout>(N, false, false, kLdsBudget);   // the placement of vlg_deptree_inside
-    const DepLayout L(N, false, false, mode);
-    if (L.lds_bytes + kSampleStackBytes > kLdsBudget)
+    const DpPlan p = dp_plan<DepLayout>(N, false, false);   // the plan of vlg_deptree_inside
+    const int Y = sample_blocks(p, B, S);
+    if (p.lds_bytes + kSampleStackBytes > kLdsBudget)
         return set_error(VLG_ERR_SHAPE, "deptree_sample: N=%d leaves no LDS for the walk's stacks", N);   // (not reached for N <= 255)
-    const size_t need = L.ws_bytes * (size_t)B * Y;
-    if (need > ws_bytes || (need && !ws))
-        return set_error(VLG_ERR_WORKSPACE, "deptree_sample: N=%d needs a %zu-byte workspace (got %zu): vlg_workspace_bytes("
-                         "VLG_OP_DEPTREE_INSIDE, B * vlg_deptree_sample_blocks(B, N, S), N, 0)", N, need, ws_bytes);
-    const SampleArgs a{arc, lengths, B, N, S, Y, rng, site, u, heads, logp, logZ, ws, L.ws_bytes, L.lds_bytes, (hipStream_t)stream};
-    const int m = mode == 0 && N <= kShortN ? kModeShort : mode;
-    return in_dtype == VLG_F32 ? launch_sample_mode<F32In>(m, a) : launch_sample_mode<BF16In>(m, a);
+    // one slice per block of the (B, Y) grid: vlg_workspace_bytes(VLG_OP_DEPTREE_INSIDE, B * vlg_deptree_sample_blocks(B, N, S), N, 0)
+    if (int e = check_dp_workspace("deptree_sample", N, p, (size_t)B * Y, ws, ws_bytes)) return e;
+    const SampleArgs a{arc, lengths, B, N, S, Y, rng, site, u, heads, logp, logZ, ws, p.ws_stride, p.lds_bytes, (hipStream_t)stream};
+    return in_dtype == VLG_F32 ? launch_sample_mode<F32In>(p.image, a) : launch_sample_mode<BF16In>(p.image, a);
 }
 
 }  // extern "C"
