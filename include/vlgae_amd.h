@@ -41,7 +41,9 @@ enum {
     VLG_OP_DMV1O_INSIDE = 0,
     VLG_OP_DMV1O_INSIDE_OUTSIDE = 1,
     VLG_OP_DEPTREE_INSIDE = 2,
-    VLG_OP_DEPTREE_INSIDE_OUTSIDE = 3
+    VLG_OP_DEPTREE_INSIDE_OUTSIDE = 3,
+    VLG_OP_DEPTREE_EXPECT = 4,       /* vlg_deptree_expect, forward only (mu == hv == NULL) */
+    VLG_OP_DEPTREE_EXPECT_GRAD = 5   /* vlg_deptree_expect with mu and / or hv */
 };
 enum {
     VLG_ERR_SHAPE = 0x1001,     /* mirrors the reference's shape asserts (deptree.py:149,154) */
@@ -109,6 +111,22 @@ int vlg_deptree_decode(const void* arc, const int64_t* lengths, int B, int N, in
 int vlg_deptree_sample(const void* arc, const int64_t* lengths, int B, int N, int in_dtype, int S, const uint64_t* rng, unsigned site,
                        const float* u, int64_t* heads, float* logp, float* logZ, void* ws, size_t ws_bytes, void* stream);
 int vlg_deptree_sample_blocks(int B, int N, int S);
+
+/* Expectations under the projective CRF, on the device: the DepTree inside(-outside) pass in dual numbers, one launch.  Every chart
+ * cell carries its derivative along the direction d = v - v_sub in potential space (rule: DESIGN.md section 2, "Expectations").
+ *   arc [B,N,N] in in_dtype; v, v_sub [B,N,N] in v_dtype (VLG_F32 / VLG_BF16), each optional: NULL reads as 0.  d is forced to 0 where
+ *   the arc is forbidden (-inf, or below the clamp floor) and outside the sentence; elsewhere it must be finite.
+ *   logZ [B] (required); ev [B] = <mu, d> (optional); mu [B,N,N] arc marginals (optional); hv [B,N,N] = (Hessian of logZ) d (optional):
+ *   float32, fully written, zeros on the diagonal and outside the sentence.  An invalid length gives logZ = ev = NaN, mu = hv = 0.
+ *   These are what the reference's entropy / cross_entropy / kl / risk (distributions.py:79-114) and their gradients are made of:
+ *     E_p[<c, tree>]: d = c        value ev                 d/d arc = hv    d/d c = mu
+ *     H[p]:           d = arc_p    value logZ - ev          d/d arc = -hv
+ *     H[p,q]:         d = arc_q    value logZ_q - ev        d/d arc_p = -hv  d/d arc_q = mu_q - mu_p
+ *     KL[p||q]:       d = arc_q - arc_p   value logZ_q - logZ_p - ev   (same gradients)
+ *   mu == hv == NULL runs the inside pass only: workspace vlg_workspace_bytes(VLG_OP_DEPTREE_EXPECT, B, N, 0); otherwise
+ *   VLG_OP_DEPTREE_EXPECT_GRAD.  VLG_ERR_SHAPE for N outside 2 ... 255, VLG_ERR_DTYPE, VLG_ERR_ARG for NULL arc / logZ, VLG_ERR_WORKSPACE. */
+int vlg_deptree_expect(const void* arc, const void* v, const void* v_sub, const int64_t* lengths, int B, int N, int in_dtype, int v_dtype,
+                       float* logZ, float* ev, float* mu, float* hv, void* ws, size_t ws_bytes, void* stream);
 
 /* The MBR decode of ldndmv.py:294-299 straight from the DMV1o arc marginals: DependencyCRF(marginals.sum(-1)).argmax.  marginals
  * [B,N,N,2] float32 (head, child, valence), as vlg_dmv1o_inside_outside / vlg_dmv1o_marginals_viterbi write grad_attach; the valence sum

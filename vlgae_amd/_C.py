@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("VLGAE_AMD_LIB") or os.path.join(_PKG, "_lib", "libvlg
 F32, BF16, F64 = 0, 1, 2
 SEMIRING_LOG, SEMIRING_MAX = 0, 1
 OP_DMV1O_INSIDE, OP_DMV1O_INSIDE_OUTSIDE, OP_DEPTREE_INSIDE, OP_DEPTREE_INSIDE_OUTSIDE = 0, 1, 2, 3
+OP_DEPTREE_EXPECT, OP_DEPTREE_EXPECT_GRAD = 4, 5
 
 _vp, _i, _f, _sz, _ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_longlong
 
@@ -63,6 +64,7 @@ SIGNATURES = {
     "vlg_deptree_mbr_decode": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "vlg_deptree_sample": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, ctypes.c_uint, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vlg_deptree_sample_blocks": (_i, [_i, _i, _i]),
+    "vlg_deptree_expect": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vlg_eval_metrics_workspace": (_sz, [_i]),
     "vlg_eval_metrics": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "vlg_dmv1o_marginals_viterbi_supported": (_i, [_i]),

@@ -280,6 +280,8 @@ size_t vlg_workspace_bytes(int op, int B, int N, int semiring) {
         case VLG_OP_DMV1O_INSIDE_OUTSIDE: return dp_plan<DmvLayout>(N, true, is_max).ws_stride * B;
         case VLG_OP_DEPTREE_INSIDE: return dp_plan<DepLayout>(N, false, is_max).ws_stride * B;
         case VLG_OP_DEPTREE_INSIDE_OUTSIDE: return dp_plan<DepLayout>(N, true, is_max).ws_stride * B;
+        case VLG_OP_DEPTREE_EXPECT: return is_max ? 0 : dp_plan<ExpectLayout>(N, false, false).ws_stride * B;   // Log semiring only
+        case VLG_OP_DEPTREE_EXPECT_GRAD: return is_max ? 0 : dp_plan<ExpectLayout>(N, true, false).ws_stride * B;
         default: return 0;
     }
 }

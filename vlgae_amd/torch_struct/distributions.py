@@ -20,7 +20,8 @@ def _out_of_scope(name):
     raise NotImplementedError(
         f"StructDistribution.{name}: no caller in VLGAE uses it (only partition / max / argmax / marginals are "
         "reached; SURVEY.md section 2) -- outside the MI355X hot path this package implements.  (Drawing trees is "
-        "implemented for DependencyCRF as `sample_heads` / `heads_to_parts`.)")
+        "implemented for DependencyCRF as `sample_heads` / `heads_to_parts`; entropy, cross-entropy, KL and expected scores as "
+        "`tree_entropy` / `tree_cross_entropy` / `tree_kl` / `expected_score`.)")
 
 
 class StructDistribution(Distribution):
@@ -236,6 +237,25 @@ class DependencyCRF(StructDistribution):
         if own:
             rng.advance()
         return (heads, logp) if return_log_prob else heads
+
+    # -- expectations (extension: one dual-number inside-outside launch each, exact gradients; functional.deptree_expect) ------------
+    # The reference's names (`entropy`, `cross_entropy`, `kl`, `risk`, distributions.py:79-114) stay out of scope under those names,
+    # as `sample` does next to `sample_heads`.  All return [B] and are differentiable once with respect to every potential.
+    def expected_score(self, cost):
+        "E_p[<cost, tree>] for arc costs [B,N,N]: the reference's `risk(cost)`."
+        return F.deptree_expected_score(self.log_potentials, self.lengths, cost)
+
+    def tree_entropy(self):
+        "H[p]: the reference's `entropy`."
+        return F.deptree_entropy(self.log_potentials, self.lengths)
+
+    def tree_cross_entropy(self, other):
+        "H[p, q] with q = `other` (a DependencyCRF over the same sentences): the reference's `cross_entropy(other)`."
+        return F.deptree_cross_entropy(self.log_potentials, other.log_potentials, self.lengths)
+
+    def tree_kl(self, other):
+        "KL[p || q] = H[p, q] - H[p]; exactly 0 with zero gradients when both hold the same potentials."
+        return F.deptree_kl(self.log_potentials, other.log_potentials, self.lengths)
 
     @staticmethod
     def heads_to_parts(heads, lengths=None):

@@ -446,6 +446,144 @@ def deptree_sum(arc, lengths, semiring):
     return _DepTreeSum.apply(arc, lengths, semiring)
 
 
+def deptree_expect(arc, lengths, v=None, v_sub=None, want_mu=False, want_hv=False):
+    """Raw launcher of the dual-number DepTree pass (vlg_deptree_expect).  arc [B,N,N]; v, v_sub [B,N,N] or None (= 0): the direction is
+    v - v_sub.  Returns (logZ [B], ev [B] = <mu, v - v_sub>, mu [B,N,N] or None, hv [B,N,N] = (Hessian of logZ)(v - v_sub) or None),
+    all float32.  want_mu / want_hv select the inside-outside image; without them only the inside pass runs."""
+    _C.require_gpu(arc, "deptree_expect")
+    if arc.dim() != 3:
+        raise ValueError("potentials must have dim of 3 (unlabeled)")
+    B, N, N2 = arc.shape
+    assert N == N2, "Non-square potentials"
+    dt, arc_c = _C.in_dtype(arc)
+    vs = [t for t in (v, v_sub) if t is not None]
+    for t in vs:
+        _C.require_gpu(t, "deptree_expect")
+        if tuple(t.shape) != (B, N, N):
+            raise ValueError(f"direction must be [B,N,N] = {(B, N, N)}, got {tuple(t.shape)}")
+    vdt = _C.F32
+    if vs:   # both directions in one storage type: bf16 only when every one given is bf16
+        if all(t.dtype == torch.bfloat16 for t in vs):
+            vdt = _C.BF16
+        else:
+            v, v_sub = (None if t is None else t.detach().float() for t in (v, v_sub))
+        v, v_sub = (None if t is None else (t if t.is_contiguous() else t.contiguous()) for t in (v, v_sub))
+    lengths = _lengths(lengths, B, arc.device, allow_none=True)
+    grad = want_mu or want_hv
+    (logZ, ev, mu, hv), _ = _C.alloc_f32(arc.device, [(B,), (B,), (B, N, N) if want_mu else None, (B, N, N) if want_hv else None])
+    ws, nb = _workspace(_C.OP_DEPTREE_EXPECT_GRAD if grad else _C.OP_DEPTREE_EXPECT, B, N, _C.SEMIRING_LOG, arc.device)
+    _C.check(_C.lib().vlg_deptree_expect(_C.ptr(arc_c), _C.ptr(v), _C.ptr(v_sub), _C.ptr(lengths), B, N, dt, vdt, _C.ptr(logZ), _C.ptr(ev),
+                                         _C.ptr(mu), _C.ptr(hv), _C.ptr(ws), nb, _C.stream_of(arc)), "deptree_expect")
+    return logZ, ev, mu, hv
+
+
+def _out_dtype(t):
+    return t.dtype if t.dtype == torch.float64 else torch.float32
+
+
+class _DepTreeExpectedScore(torch.autograd.Function):
+    """E_p[<cost, tree>] (the reference's `risk`): value ev, d/d arc = hv = Cov(tree, <cost, tree>), d/d cost = mu."""
+
+    @staticmethod
+    def forward(ctx, arc, lengths, cost):
+        wa, wc = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
+        _, ev, mu, hv = deptree_expect(arc, lengths, v=cost, want_mu=wc, want_hv=wa)
+        ctx.save_for_backward(hv, mu)
+        ctx.in_dtypes = (arc.dtype, cost.dtype)
+        return ev.to(_out_dtype(arc))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        hv, mu = ctx.saved_tensors
+        ga, gc = _scale_counts(hv, mu, grad_out, *ctx.in_dtypes)
+        return ga, None, gc
+
+
+class _DepTreeEntropy(torch.autograd.Function):
+    """H[p] = logZ - <mu, arc>: the direction is the distribution's own potentials; d/d arc = -hv."""
+
+    @staticmethod
+    def forward(ctx, arc, lengths):
+        want = ctx.needs_input_grad[0]
+        logZ, ev, _, hv = deptree_expect(arc, lengths, v=arc, want_hv=want)
+        if want:
+            ctx.save_for_backward(hv)
+        ctx.in_dtype = arc.dtype
+        return (logZ - ev).to(_out_dtype(arc))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        (hv,) = ctx.saved_tensors
+        return _scale_counts(hv, None, -grad_out, ctx.in_dtype, ctx.in_dtype)[0], None
+
+
+def _deptree_pq(ctx, arc_p, arc_q, lengths, v_sub):
+    """The two launches cross-entropy and KL share: p along v = arc_q (- v_sub), q with no direction.  The q side runs the outside pass
+    only when arc_q wants a gradient (a fixed q costs one inside pass): the value pass of the inside-only image and of the
+    inside-outside image is the same sequence of operations (vlg_dp_expect.h: expect_fw_span), so on equal potentials the two logZ
+    agree bit for bit whichever images ran."""
+    wp, wq = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    logZ_p, ev, mu_p, hv = deptree_expect(arc_p, lengths, v=arc_q, v_sub=v_sub, want_mu=wq, want_hv=wp)
+    logZ_q, _, mu_q, _ = deptree_expect(arc_q, lengths, want_mu=wq)
+    if wq:
+        mu_p.sub_(mu_q)          # in place: -(d/d arc_q) = mu_p - mu_q, scaled together with hv by -grad in backward
+    ctx.save_for_backward(hv if wp else None, mu_p if wq else None)
+    ctx.in_dtypes = (arc_p.dtype, arc_q.dtype)
+    return logZ_p, logZ_q, ev
+
+
+def _deptree_pq_backward(ctx, grad_out):
+    hv, dmu = ctx.saved_tensors
+    gp, gq = _scale_counts(hv, dmu, -grad_out, *ctx.in_dtypes)
+    return gp, gq, None
+
+
+class _DepTreeCrossEntropy(torch.autograd.Function):
+    """H[p,q] = logZ_q - <mu_p, arc_q>; d/d arc_p = -hv, d/d arc_q = mu_q - mu_p."""
+
+    @staticmethod
+    def forward(ctx, arc_p, arc_q, lengths):
+        _, logZ_q, ev = _deptree_pq(ctx, arc_p, arc_q, lengths, None)
+        return (logZ_q - ev).to(_out_dtype(arc_p))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        return _deptree_pq_backward(ctx, grad_out)
+
+
+class _DepTreeKL(torch.autograd.Function):
+    """KL[p||q] = logZ_q - logZ_p - <mu_p, arc_q - arc_p> (the subtraction is the kernel's v - v_sub); gradients as for H[p,q]."""
+
+    @staticmethod
+    def forward(ctx, arc_p, arc_q, lengths):
+        logZ_p, logZ_q, ev = _deptree_pq(ctx, arc_p, arc_q, lengths, arc_p)
+        return (logZ_q - logZ_p - ev).to(_out_dtype(arc_p))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        return _deptree_pq_backward(ctx, grad_out)
+
+
+def deptree_expected_score(arc, lengths, cost):
+    return _DepTreeExpectedScore.apply(arc, lengths, cost)
+
+
+def deptree_entropy(arc, lengths):
+    return _DepTreeEntropy.apply(arc, lengths)
+
+
+def deptree_cross_entropy(arc_p, arc_q, lengths):
+    return _DepTreeCrossEntropy.apply(arc_p, arc_q, lengths)
+
+
+def deptree_kl(arc_p, arc_q, lengths):
+    return _DepTreeKL.apply(arc_p, arc_q, lengths)
+
+
 def dmv1o_merge(dec, attach, root, one=0.0, zero=NEGINF):
     """DMV1o.merge (distributions.py:253-265): root-augmented potentials, always float32."""
     _C.require_gpu(dec, "dmv1o_merge")
