@@ -441,12 +441,8 @@ VLG_HD void dmv_fw_width(const DmvCtx& c, int w, int lgr, int t, int nd, X& x) {
         if (X::kSkipDeadWaves && (base + ((t & ~63) >> lg)) >= spans) continue;   // whole wavefront past the last span
         const int D = VLG_MUL24(i, c.P + 1);
         constexpr bool NC = LONGSPAN != 1 && X::kChartsInLds;
-        if constexpr (LONGSPAN == kSpansShort && LG >= 0) {   // N <= kShortN: this segment never sees more than TM split points per lane
-            constexpr int TM = short_tmax(LG, kShortN, VLG_DP_LANES_FW);
-            if (TM == 1 || T == 1) dmv_fw_span<SR, BWD, DIR, 1, X, NC>(c, w, G, D, live, rr, x);
-            else if (TM == 2 || T == 2) dmv_fw_span<SR, BWD, DIR, 2, X, NC>(c, w, G, D, live, rr, x);
-            else dmv_fw_span<SR, BWD, DIR, 3, X, NC>(c, w, G, D, live, rr, x);
-        } else if (T == 1) dmv_fw_span<SR, BWD, DIR, 1, X, NC>(c, w, G, D, live, rr, x);
+        static_assert(LONGSPAN != kSpansShort, "the short image's inside pass is dmv_fw_segment_p");
+        if (T == 1) dmv_fw_span<SR, BWD, DIR, 1, X, NC>(c, w, G, D, live, rr, x);
         else if (T == 2) dmv_fw_span<SR, BWD, DIR, 2, X, NC>(c, w, G, D, live, rr, x);
         else if (T == 3) dmv_fw_span<SR, BWD, DIR, 3, X, NC>(c, w, G, D, live, rr, x);
         else if (T == 4) dmv_fw_span<SR, BWD, DIR, 4, X, NC>(c, w, G, D, live, rr, x);
@@ -472,7 +468,7 @@ template <int SR, bool BWD, int LG, int LONGSPAN, typename X>
 VLG_HD void dmv_fw_segment(const DmvCtx& c, int w0, int w1, int tid, int nt, X& x) {
     const int nd = nt >> 1;                 // lanes per direction
     const bool right = x.uniform(tid >= nd);   // wave-uniform on the device (nd is a multiple of 64)
-    const int t = dir_lane<VLG_MIRROR_RIGHT && LONGSPAN == kSpansShort>(tid, nd, right);
+    const int t = right ? tid - nd : tid;
     for (int w = w0; w < w1; ++w) {
         if (right) dmv_fw_width<SR, BWD, 1, LG, LONGSPAN>(c, w, LG, t, nd, x);
         else dmv_fw_width<SR, BWD, 0, LG, LONGSPAN>(c, w, LG, t, nd, x);
@@ -482,17 +478,30 @@ VLG_HD void dmv_fw_segment(const DmvCtx& c, int w0, int w1, int tid, int nt, X& 
     }
 }
 
+template <int SR, bool BWD, int LG, typename X>
+VLG_HD void dmv_fw_segment_p(const DmvCtx& c, int w0, int w1, int tid, int nt, X& x);   // the short image's form: with the address plans, below
+
 template <int SR, bool BWD, int LONGSPAN, typename X>
 VLG_HD void dmv_fw_all(const DmvCtx& c, int tid, int nt, X& x) {
     const Sched sc = make_sched(c.Ne, nt >> 1, VLG_DP_LANES_FW);
     VLG_WSTAMP(x, 0, 0, 1);   // the pass starts: the "release" before width 1
-    dmv_fw_segment<SR, BWD, 0, LONGSPAN>(c, sc.first[0], sc.first[1], tid, nt, x);
-    dmv_fw_segment<SR, BWD, 1, LONGSPAN>(c, sc.first[1], sc.first[2], tid, nt, x);
-    dmv_fw_segment<SR, BWD, 2, LONGSPAN>(c, sc.first[2], sc.first[3], tid, nt, x);
-    dmv_fw_segment<SR, BWD, 3, LONGSPAN>(c, sc.first[3], sc.first[4], tid, nt, x);
-    dmv_fw_segment<SR, BWD, 4, LONGSPAN>(c, sc.first[4], sc.first[5], tid, nt, x);
-    dmv_fw_segment<SR, BWD, 5, LONGSPAN>(c, sc.first[5], sc.first[6], tid, nt, x);
-    dmv_fw_segment<SR, BWD, 6, LONGSPAN>(c, sc.first[6], sc.first[7], tid, nt, x);
+    if constexpr (LONGSPAN == kSpansShort) {   // the short-sentence image: addresses built per segment and stepped per width (dmv_fw_segment_p)
+        dmv_fw_segment_p<SR, BWD, 0>(c, sc.first[0], sc.first[1], tid, nt, x);
+        dmv_fw_segment_p<SR, BWD, 1>(c, sc.first[1], sc.first[2], tid, nt, x);
+        dmv_fw_segment_p<SR, BWD, 2>(c, sc.first[2], sc.first[3], tid, nt, x);
+        dmv_fw_segment_p<SR, BWD, 3>(c, sc.first[3], sc.first[4], tid, nt, x);
+        dmv_fw_segment_p<SR, BWD, 4>(c, sc.first[4], sc.first[5], tid, nt, x);
+        dmv_fw_segment_p<SR, BWD, 5>(c, sc.first[5], sc.first[6], tid, nt, x);
+        dmv_fw_segment_p<SR, BWD, 6>(c, sc.first[6], sc.first[7], tid, nt, x);
+    } else {
+        dmv_fw_segment<SR, BWD, 0, LONGSPAN>(c, sc.first[0], sc.first[1], tid, nt, x);
+        dmv_fw_segment<SR, BWD, 1, LONGSPAN>(c, sc.first[1], sc.first[2], tid, nt, x);
+        dmv_fw_segment<SR, BWD, 2, LONGSPAN>(c, sc.first[2], sc.first[3], tid, nt, x);
+        dmv_fw_segment<SR, BWD, 3, LONGSPAN>(c, sc.first[3], sc.first[4], tid, nt, x);
+        dmv_fw_segment<SR, BWD, 4, LONGSPAN>(c, sc.first[4], sc.first[5], tid, nt, x);
+        dmv_fw_segment<SR, BWD, 5, LONGSPAN>(c, sc.first[5], sc.first[6], tid, nt, x);
+        dmv_fw_segment<SR, BWD, 6, LONGSPAN>(c, sc.first[6], sc.first[7], tid, nt, x);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -655,9 +664,9 @@ struct BwVals {
 };
 
 template <typename T>
-VLG_HD T bw_ld(const char* p, int off = 0) { return *reinterpret_cast<const T*>(p + off); }
+VLG_HD T addr_ld(const char* p, int off = 0) { return *reinterpret_cast<const T*>(p + off); }
 template <typename T>
-VLG_HD void bw_st(char* p, int off, T v) { *reinterpret_cast<T*>(p + off) = v; }
+VLG_HD void addr_st(char* p, int off, T v) { *reinterpret_cast<T*>(p + off) = v; }
 
 struct BwAddr {
     const char *vC, *vI, *vS, *vSU, *vUU, *vVV, *vXA, *vXB;   // value charts: own C / I cell, tape cell, partner, the four walks
@@ -706,27 +715,200 @@ VLG_HD BwAddr dmv_bw_addr(const DmvCtx& c, int w, int D, int rr, bool right, X& 
     return a;
 }
 
+// ---- Inside pass, short-sentence image: the same plan (round 9) -------------------------------------------------------------------
+// dmv_fw_width rebuilt rr, slot, D = slot (P + 1), DW and the seven cell indices at every width, and dmv_fw_span turned each into an
+// address per access.  In the short image a lane group holds ONE span per width for a whole segment -- segment k >= 1 begins where
+// (Ne - w) 2^k <= cap <= the lanes of a direction (make_sched), and segment 0 has Ne - w <= kShortN - 1 spans of one lane each, fewer
+// than the lanes of a direction (a multiple of 64, for dir_lane) -- so dmv_fw_width's `base` loop runs once and the table of the
+// outside pass extends to the inside pass, the widths ascending:
+//                                    DIR 0 (left)                      DIR 1 (right)
+//   eA: CR(i, i+r)      (a)          D + 1 + rr        [0]             D + 1 + rr          [0]     term u: + u G
+//   eB: CL(j, i+r+1)    (b)          D + wP + 1 + rr   [P]             D + wP + 1 + rr     [P]     term u: + u G
+//   eU: column walk     (uu)         D + rr P          [0]             D + P + w + 1 + rr P  [1]   term u: + u G P
+//   eV: row walk        (vv)         D + wP + rr       [P]             D + 2 + rr          [0]     term u: + u G
+//   own slot kO (I and C)            D + wP            [P]             D + w + 1           [1]
+//   same-width partner cX            D                 [0]             D + wP + w + 1      [P + 1]
+//   tape cell kS (S)                 D + wP            [P]             D + w               [1]
+// FwAddr holds one pinned byte address per row (own slot: one for I, one for C), a width steps the five (left) or six (right) that
+// move, and the direction is a template parameter of everything that touches them (as a run-time value the inside pass measured
+// 33.4 -> 39.4 us): each direction has its own width loops, so a stepped address is carried round its loop without a merge.
+// A lane with no span at the segment's first width shadows span 0, as before; one whose span ends inside the segment (the spans of a
+// width shrink as w grows) keeps its addresses: its reads fall on rows past Ne -- all below D + wP + rP + P + w + 2, the bound the
+// host driver's slack is sized by -- it never stores, and its whole group is dead with it, so no live butterfly sees what it read.
+template <int DIR>
+struct FwAddr {
+    const char *eA, *eB, *eU, *eV, *cX;   // the four walks at this lane's first term, the same-width partner
+    char *oI, *oC, *oS;                   // own slot in I (read: attach + dec, then written) and in C, tape cell in S
+    int p8, p4;                           // byte size of a chart row of 8- / 4-byte cells (wave-uniform)
+    int gp8;                              // column-walk stride between a lane's terms: G P cells of 8 bytes
+    VLG_HDM void step() {                 // w -> w + 1
+        eB += p8;
+        if (DIR == 0) { eV += p8; oI += p8; oC += p8; oS += p4; }
+        else { eU += 8; oI += 8; oC += 8; oS += 4; cX += p8 + 8; }
+    }
+};
+
+template <int DIR, int G, bool TAPE, typename X>
+VLG_HD FwAddr<DIR> dmv_fw_addr(const DmvCtx& c, int w, int D, int rr, X& x) {
+    const int P = c.P, DW = D + VLG_MUL24(w, P), q = D + rr, qP = D + VLG_MUL24(rr, P);
+    const int kO = DIR == 0 ? DW : D + w + 1;
+    const char* C = reinterpret_cast<const char*>(c.C);
+    const char* I = reinterpret_cast<const char*>(c.I);
+    FwAddr<DIR> a;
+    a.eA = x.pin(C + 8 * (q + 1) + (DIR == 0 ? 4 : 0));            // .NC for SL, .HC for SR
+    a.eB = x.pin(C + 8 * (DW + rr + 1) + (DIR == 0 ? 0 : 4));      // .HC for SL, .NC for SR
+    a.eU = x.pin(C + 8 * (DIR == 0 ? qP : qP + P + w + 1) + 4);    // CL(i+r, i).NC | CR(i+1+r, j).NC
+    a.eV = x.pin(I + 8 * (DIR == 0 ? DW + rr : q + 2));            // IL(j, i+r) | IR(i, i+1+r)
+    a.cX = x.pin(C + 8 * (DIR == 0 ? D : DW + w + 1) + 4);         // CL(i,i).NC | CR(j,j).NC
+    a.oI = x.pin(reinterpret_cast<char*>(c.I) + 8 * kO);
+    a.oC = x.pin(reinterpret_cast<char*>(c.C) + 8 * kO);
+    a.oS = nullptr;
+    if constexpr (TAPE) a.oS = x.pin(reinterpret_cast<char*>(c.S) + 4 * (DIR == 0 ? DW : D + w));
+    a.p8 = x.uniform(8 * P);
+    a.p4 = x.uniform(4 * P);
+    a.gp8 = 8 * G * P;
+    return a;
+}
+
+// dmv_fw_span's TU > 0 form on the stepped addresses: the same adds, maxes, exponentials and logarithms on the same operands in the
+// same order.  What is gone are selects.  The caller runs this body only at widths with EXACTLY TU split points per lane,
+// TU = ceil(w / G), so w > (TU - 1) G and every term u < TU - 1 of every lane is in range: r = rr + u G <= (TU - 1) G - 1 <= w - 2.
+// That is both `r < w` and the right direction's `r <= w - 2`; the left direction's `r >= 1` holds for every term but the first
+// (u >= 1: r >= G >= 1).  So only the last term is compared with w (the right direction: with w - 1 as well), and only the left
+// direction's first term with 1.  Max semiring: am[] is rr + u G as before, so first-index-wins is untouched.
+template <int SR, bool BWD, int DIR, int G, int TU, typename X>
+VLG_HD void dmv_fw_span_p(const DmvCtx& c, const FwAddr<DIR>& a, int w, bool live, bool root_row, int rr, int D, X& x) {
+    const float2 aX = addr_ld<float2>(a.oI);   // attach + dec[...,GO], staged at load
+    const float cX = addr_ld<float>(a.cX);
+    float m[3], s[3] = {0.f, 0.f, 0.f};
+    int am[3];
+    float t[TU][3];
+#pragma unroll
+    for (int u = 0; u < TU; ++u) {
+        const int r = rr + u * G;
+        const float av = addr_ld<float>(a.eA, u * G * 8), bv = addr_ld<float>(a.eB, u * G * 8);
+        const float uu = addr_ld<float>(a.eU, u * a.gp8);
+        const float2 vv = addr_ld<float2>(a.eV, u * G * 8);
+        const bool last = u == TU - 1;
+        const bool v0 = last ? r < w : true;
+        const bool v1 = DIR == 0 ? (v0 && (u == 0 ? r >= 1 : true)) : (last ? r <= w - 2 : true);
+        t[u][0] = v0 ? av + bv : VLG_LOWEST;
+        t[u][1] = v1 ? uu + vv.x : VLG_LOWEST;
+        t[u][2] = v1 ? uu + vv.y : VLG_LOWEST;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        m[k] = t[0][k];
+        am[k] = rr;
+        if (SR == VLG_SR_LOG) {
+#pragma unroll
+            for (int u = 1; u < TU; ++u) m[k] = fmaxf(m[k], t[u][k]);
+        } else {
+#pragma unroll
+            for (int u = 1; u < TU; ++u)
+                if (t[u][k] > m[k]) { m[k] = t[u][k]; am[k] = rr + u * G; }   // strict: first index wins ties
+        }
+    }
+    if (SR == VLG_SR_MAX) x.template allreduce_argmax<3>(m, am, G);
+    else x.template allreduce_max<3>(m, G);
+    if (SR == VLG_SR_LOG) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            s[k] = VLG_EXP(t[0][k] - m[k]);
+#pragma unroll
+            for (int u = 1; u < TU; ++u) s[k] += VLG_EXP(t[u][k] - m[k]);   // masked terms: 2^(-3e38) = 0
+        }
+        x.template allreduce_sum<3>(s, G);
+    }
+    const float Sv = SR == VLG_SR_LOG ? m[0] + VLG_LOG(s[0]) : m[0];       // SL | SR
+    const float2 In = make_float2(aX.x + Sv, aX.y + Sv);                    // IL(j,i) | IR(i,j)
+    int b0, b1;
+    float Cx = fold_term<SR>(m[1], s[1], am[1], cX + In.x, DIR == 0 ? 0 : w - 1, DIR == 0, b0);
+    float Cy = fold_term<SR>(m[2], s[2], am[2], cX + In.y, DIR == 0 ? 0 : w - 1, DIR == 0, b1);
+    if (DIR == 1 && root_row && w != c.len) { Cx = VLG_NEGINF; Cy = VLG_NEGINF; }   // single root, dmv.py:63
+    if (live && rr == 0) {
+        addr_st(a.oI, 0, In);
+        addr_st(a.oC, 0, make_float2(Cx, Cy));
+        if (BWD) {
+            if (SR != VLG_SR_MAX) addr_st(a.oS, 0, Sv);   // the tape of the outside replay
+            if (SR == VLG_SR_MAX) {                       // back-pointer bytes: one lane per span, index arithmetic stays in this branch
+                const int DW = D + VLG_MUL24(w, c.P), kO = DIR == 0 ? DW : D + w + 1, kS = DIR == 0 ? DW : D + w;
+                c.bpS[kS] = (unsigned char)am[0];
+                c.bpC[kO * 2] = (unsigned char)b0;
+                c.bpC[kO * 2 + 1] = (unsigned char)b1;
+            }
+        }
+    }
+}
+
+// the widths wa ... wb - 1 of a segment that have TU split points per lane: one body, one barrier per width
+template <int SR, bool BWD, int DIR, int LG, int TU, typename X>
+VLG_HD void dmv_fw_piece_p(const DmvCtx& c, FwAddr<DIR>& a, int wa, int wb, int slot, int wslot, int rr, int D, X& x) {
+    constexpr int G = 1 << LG;
+    for (int w = wa; w < wb; ++w) {
+        const int spans = x.uniform(c.Ne - w);
+        const bool live = slot < spans;
+        // (wave-uniform) a wavefront without a span of this width skips the body, not the step and the barrier
+        if (!(X::kSkipDeadWaves && wslot >= spans)) dmv_fw_span_p<SR, BWD, DIR, G, TU>(c, a, w, live, slot == 0, rr, D, x);
+        a.step();
+        VLG_WSTAMP(x, 0, w, 0);
+        x.sync();
+        VLG_WSTAMP(x, 0, w, 1);
+    }
+}
+
+template <int SR, bool BWD, int DIR, int LG, typename X>
+VLG_HD void dmv_fw_dir_p(const DmvCtx& c, int w0, int w1, int t, X& x) {
+    constexpr int G = 1 << LG, TM = short_tmax(LG, kShortN, VLG_DP_LANES_FW);
+    const int rr = t & (G - 1), slot = t >> LG, wslot = (t & ~63) >> LG;   // wslot: the first span of this lane's wavefront
+    const int D = slot < c.Ne - w0 ? VLG_MUL24(slot, c.P + 1) : 0;         // no span at any width of the segment: shadow span 0
+    FwAddr<DIR> a = dmv_fw_addr<DIR, G, BWD && SR != VLG_SR_MAX>(c, w0, D, rr, x);
+    // T = ceil(w / G) does not fall as w grows: the widths of the segment with T = k are ((k - 1) G, k G], run one after the other,
+    // each by the body unrolled for exactly k terms (in the inside pass a spare term costs three exponentials on the chain).  Both
+    // directions walk the same pieces: the same barriers.
+#pragma unroll
+    for (int k = 1; k <= TM; ++k) {
+        const int lo = (k - 1) * G + 1, hi = k == TM ? w1 : k * G + 1;
+        const int wa = w0 > lo ? w0 : lo, wb = w1 < hi ? w1 : hi;
+        if (k == 1) dmv_fw_piece_p<SR, BWD, DIR, LG, 1>(c, a, wa, wb, slot, wslot, rr, D, x);
+        else if (k == 2) dmv_fw_piece_p<SR, BWD, DIR, LG, 2>(c, a, wa, wb, slot, wslot, rr, D, x);
+        else dmv_fw_piece_p<SR, BWD, DIR, LG, 3>(c, a, wa, wb, slot, wslot, rr, D, x);
+    }
+}
+
+// all widths of one segment of the short-sentence image
+template <int SR, bool BWD, int LG, typename X>
+VLG_HD void dmv_fw_segment_p(const DmvCtx& c, int w0, int w1, int tid, int nt, X& x) {
+    static_assert(short_tmax(LG, kShortN, VLG_DP_LANES_FW) <= 3, "dmv_fw_dir_p's pieces end at three split points per lane");
+    if (w1 <= w0) return;
+    const int nd = nt >> 1;
+    const bool right = x.uniform(tid >= nd);   // taken once per segment: the direction never reaches a width loop
+    const int t = dir_lane<VLG_MIRROR_RIGHT>(tid, nd, right);
+    if (right) dmv_fw_dir_p<SR, BWD, 1, LG>(c, w0, w1, t, x);
+    else dmv_fw_dir_p<SR, BWD, 0, LG>(c, w0, w1, t, x);
+}
+
 // the value reads of one width: the own cells and TM terms
 template <int G, int TM>
 VLG_HD void dmv_bw_load_vals(const BwAddr& a, BwVals<TM>& v) {
-    v.oc = bw_ld<float2>(a.vC);
-    v.Sv = bw_ld<float>(a.vS);
-    v.su = bw_ld<float>(a.vSU);
-    v.sv = bw_ld<float2>(a.vI);
+    v.oc = addr_ld<float2>(a.vC);
+    v.Sv = addr_ld<float>(a.vS);
+    v.su = addr_ld<float>(a.vSU);
+    v.sv = addr_ld<float2>(a.vI);
 #pragma unroll
     for (int u = 0; u < TM; ++u) {
-        v.uu[u] = bw_ld<float>(a.vUU, u * a.gp8);
-        v.vv[u] = bw_ld<float2>(a.vVV, u * G * 8);
-        v.xa[u] = bw_ld<float>(a.vXA, u * G * 8);
-        v.xb[u] = bw_ld<float>(a.vXB, u * G * 8);
+        v.uu[u] = addr_ld<float>(a.vUU, u * a.gp8);
+        v.vv[u] = addr_ld<float2>(a.vVV, u * G * 8);
+        v.xa[u] = addr_ld<float>(a.vXA, u * G * 8);
+        v.xb[u] = addr_ld<float>(a.vXB, u * G * 8);
     }
 }
 
 // One span of width w on the prefetched values `v` (Log semiring: the Max semiring's outside pass is the back-pointer walk), in two
 // halves with the refill of `v` between them (dmv_bw_segment_p).  BwAdj is what the first half hands to the second: the adjoint cells
-// it has requested and the weights' factors.  Both halves run the segment's TM terms at every width: a term past the width's last
-// split point (r >= w; widths 9 ... 16 and 3, 4 of a 40-word sentence have one) reads cells nobody uses and stores nothing -- its
-// store branch is skipped by the whole wavefront -- where one body per term count T <= TM made the outside pass twice the code, and
+// it has requested and the weights' factors.  Both halves run the caller's TM terms at every width: a term past the width's last
+// split point (r >= w; widths 3, 4 of a 40-word sentence have one, and 9 ... 16 had before dmv_bw_all cut their segment in two) reads
+// cells nobody uses and stores nothing -- its store branch is skipped by the whole wavefront -- where one body per term count T <= TM made the outside pass twice the code, and
 // the bodies' different register assignments met in moves at the loop's end.
 template <int TM>
 struct BwAdj {
@@ -739,15 +921,15 @@ struct BwAdj {
 // (adj_w = g * 2^min(t - out, 0): the factor first)
 template <int G, int TM, typename X>
 VLG_HD void dmv_bw_span_p1(const BwAddr& a, X& x, const BwVals<TM>& v, BwAdj<TM>& s) {
-    s.ga = bw_ld<float>(a.aGc);
-    s.gb = bw_ld<float2>(a.aGi);
-    s.gi_old = bw_ld<float2>(a.aI);
+    s.ga = addr_ld<float>(a.aGc);
+    s.gb = addr_ld<float2>(a.aGi);
+    s.gi_old = addr_ld<float2>(a.aI);
 #pragma unroll
     for (int u = 0; u < TM; ++u) {
-        s.o_gi[u] = bw_ld<float2>(a.aVV, u * G * 8);
-        s.o_c[u] = bw_ld<float>(a.aUU, u * a.gp4);
-        s.o_ga[u] = bw_ld<float>(a.aXA, u * G * 8);
-        s.o_gb[u] = bw_ld<float>(a.aXB, u * G * 8);
+        s.o_gi[u] = addr_ld<float2>(a.aVV, u * G * 8);
+        s.o_c[u] = addr_ld<float>(a.aUU, u * a.gp4);
+        s.o_ga[u] = addr_ld<float>(a.aXA, u * G * 8);
+        s.o_gb[u] = addr_ld<float>(a.aXB, u * G * 8);
     }
 #pragma unroll
     for (int u = 0; u < TM; ++u) {
@@ -784,20 +966,22 @@ VLG_HD void dmv_bw_span_p2(const BwAddr& a, int w, bool live, bool gc_ok, int rr
         const int r = rr + u * G;
         if (live && r < w) {
             const float w0 = gc.x * s.e0[u], w1 = gc.y * s.e1[u], ws = gs * s.es[u];
-            if (r != selfr) bw_st(a.aVV, u * G * 8, make_float2(s.o_gi[u].x + w0, s.o_gi[u].y + w1));
-            bw_st(a.aUU, u * a.gp4, s.o_c[u] + (w0 + w1));
-            bw_st(a.aXA, u * G * 8, s.o_ga[u] + ws);
-            bw_st(a.aXB, u * G * 8, s.o_gb[u] + ws);
+            if (r != selfr) addr_st(a.aVV, u * G * 8, make_float2(s.o_gi[u].x + w0, s.o_gi[u].y + w1));
+            addr_st(a.aUU, u * a.gp4, s.o_c[u] + (w0 + w1));
+            addr_st(a.aXA, u * G * 8, s.o_ga[u] + ws);
+            addr_st(a.aXB, u * G * 8, s.o_gb[u] + ws);
         }
     }
-    if (live && rr == 0) bw_st(a.aI, 0, gi);   // == d logZ / d attach[j,i,:] | attach[i,j,:]
+    if (live && rr == 0) addr_st(a.aI, 0, gi);   // == d logZ / d attach[j,i,:] | attach[i,j,:]
 }
 
 // widths w1-1 ... w0 of one segment of the short-sentence image (one span per lane group and width: (Ne - w) G <= the lanes of a direction)
-template <int SR, int LG, typename X>
+// TM: the terms per lane that the single body runs; the caller may name fewer than the segment's maximum for a run of widths that
+// all have w <= TM G (dmv_bw_all splits the LG = 3 segment so)
+template <int SR, int LG, int TM = short_tmax(LG, kShortN, VLG_DP_LANES_BW), typename X>
 VLG_HD void dmv_bw_segment_p(const DmvCtx& c, int w0, int w1, int tid, int nt, X& x) {
     constexpr int G = 1 << LG;
-    constexpr int TM = short_tmax(LG, kShortN, VLG_DP_LANES_BW);
+    static_assert(TM >= 1 && TM <= short_tmax(LG, kShortN, VLG_DP_LANES_BW), "more terms than any width of this segment has");
     if constexpr (SR == VLG_SR_MAX) return;   // never run: the Max semiring's outside pass is the back-pointer walk (dmv_run)
     if (w1 <= w0) return;
     const int nd = nt >> 1;
@@ -1024,7 +1208,16 @@ VLG_HD void dmv_bw_all(const DmvCtx& c, int tid, int nt, X& x) {
         dmv_bw_segment_p<SR, 6>(c, sc.first[6], sc.first[7], tid, nt, x);
         dmv_bw_segment_p<SR, 5>(c, sc.first[5], sc.first[6], tid, nt, x);
         dmv_bw_segment_p<SR, 4>(c, sc.first[4], sc.first[5], tid, nt, x);
-        dmv_bw_segment_p<SR, 3>(c, sc.first[3], sc.first[4], tid, nt, x);
+        {   // LG = 3 is the one segment whose widths differ in their term count by more than the last, partly filled term: 17 ... 24 have
+            // three split points per lane, 9 ... 16 two (T = ceil(w / G) <= TM - 1 <=> w <= (TM - 1) G).  The single-body form runs TM terms
+            // at every width, so it is instantiated twice and the segment cut at that width, high widths first: same stores, same
+            // operands, same order -- the piece with one term fewer only drops a term that stored nothing.
+            constexpr int TM3 = short_tmax(3, kShortN, VLG_DP_LANES_BW), kCut = (TM3 - 1) * (1 << 3) + 1;   // first width that needs TM3 terms
+            static_assert(TM3 >= 2, "a segment of one term per lane has nothing to split off");
+            const int cut = kCut < sc.first[3] ? sc.first[3] : (kCut < sc.first[4] ? kCut : sc.first[4]);
+            dmv_bw_segment_p<SR, 3>(c, cut, sc.first[4], tid, nt, x);
+            dmv_bw_segment_p<SR, 3, TM3 - 1>(c, sc.first[3], cut, tid, nt, x);
+        }
         dmv_bw_segment_p<SR, 2>(c, sc.first[2], sc.first[3], tid, nt, x);
         dmv_bw_segment_p<SR, 1>(c, sc.first[1], sc.first[2], tid, nt, x);
         dmv_bw_segment_p<SR, 0>(c, sc.first[0], sc.first[1], tid, nt, x);
