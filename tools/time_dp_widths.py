@@ -4,7 +4,8 @@
 Builds the stamped library variant (tools/build_variant.sh NAME -DVLG_STAMP=2: per-width stamps only, see DevX::wstamp) unless
 --lib names one, runs the headline launch a few times, and prints for every width of each pass, as the median over the first
 16 sentences (workgroups) of the last launch, in s_memtime cycles:
-  G, T          lanes per span and split points per lane (the schedule of vlg_dp_core.h: make_sched / group_log2)
+  G, T          lanes per span and split points per lane (the schedule of vlg_dp_core.h: make_sched / group_log2 for the inside
+                pass, the group table bw_group / bw_terms for the outside pass)
   live          wavefronts per direction that hold a span of that width (the others skip the body: kSkipDeadWaves)
   body_max      slowest wavefront: previous barrier's release -> its body's end
   body_min      fastest wavefront (a dead one when live < 4)
@@ -30,6 +31,23 @@ def group_log2(spans, w, cap):
     while lg < 6 and (1 << lg) < w and spans * (2 << lg) <= cap:
         lg += 1
     return lg
+
+
+BW_TABLE = (4, 8, 10, 12, 16, 32, 64)   # vlg_dp_core.h: bw_group -- the outside pass's lane groups in the short image
+
+
+def bw_group(spans, w, waves=4):
+    """vlg_dp_core.h: bw_piece_of -- the largest entry with spans <= waves (64 / G) and (G < 2 w or G the first entry)"""
+    G = BW_TABLE[0]
+    for g in BW_TABLE[1:]:
+        if spans <= waves * (64 // g) and g < 2 * w:
+            G = g
+    return G
+
+
+def bw_terms(G, Ne_max=41, waves=4):
+    """vlg_dp_core.h: bw_terms -- the terms per lane the piece's single body runs at every width"""
+    return max([-(-w // G) for ne in range(2, Ne_max + 1) for w in range(1, ne) if bw_group(ne - w, w, waves) == G] or [1])
 
 
 def main():
@@ -103,10 +121,15 @@ def main():
             rel = st[:, pas, w, 1, :].max(axis=1)
             body = (end - rel_prev[:, None]) % M32
             cap = 256
-            lg = group_log2(Ne - w, w, cap)
-            G = 1 << lg
-            T = (w + G - 1) >> lg
-            live = min(4, -(-((Ne - w) * G) // 64))
+            if pas == 1:      # outside: groups from the table, 64 // G of them per wavefront, the piece's terms at every width
+                G = bw_group(Ne - w, w)
+                T = bw_terms(G)
+                live = min(4, -(-(Ne - w) // (64 // G)))
+            else:             # inside: make_sched, the widths 1 and 2 as one closed piece of one lane per span
+                lg = 0 if w <= 2 else group_log2(Ne - w, w, cap)
+                G = 1 << lg
+                T = (w + G - 1) >> lg
+                live = min(4, -(-((Ne - w) * G) // 64))
             row = {"body_max": np.median(body.max(axis=1)), "body_min": np.median(body.min(axis=1)),
                    "skew": np.median((end.max(axis=1) - end.min(axis=1)) % M32), "bar": np.median((rel - end.max(axis=1)) % M32),
                    "width": np.median((rel - rel_prev) % M32)}

@@ -255,6 +255,102 @@ constexpr int short_tmax(int lg_want, int n_max, int cap) {
 static_assert(short_sentence_ok(kShortN, VLG_DP_LANES_FW) && short_sentence_ok(kShortN, VLG_DP_LANES_BW),
               "kShortN: a sentence of that length has a width with more than three split points per lane at these lane budgets");
 
+// ---- the short image's OUTSIDE pass: lane groups of any size, from a table (round 10) -----------------------------------------------
+// The outside pass has no cross-lane reduction -- within a phase every adjoint word has one owner -- so its results do not depend on
+// how spans and split points are dealt to lanes, and its groups need not be powers of two.  With powers of two the widths 17 ... 24 of
+// a 40-word sentence ran THREE terms per lane (8 lanes x 2 terms cover 16 split points, 16 lanes x 24 spans exceed a direction's 256
+// lanes); groups of 10 and 12 lanes cover them in two.  A group must still sit inside one wavefront (dmv_bw_span_p2's lockstep: the
+// own gI cell is read by all G lanes and written by lane rr == 0), so a wavefront takes 64 / G whole groups and its remaining lanes
+// idle.  The rule, for a width w with Ne - w spans on `waves` wavefronts per direction: the LARGEST entry G of the table with
+//     Ne - w <= waves (64 / G)      and      (G < 2 w  or  G is the table's first entry);
+// the second condition is group_log2's "no more lanes than split points, rounded up" (there 2^lg < 2w), waived for the smallest group
+// so that the widths 1 and 2 join its piece instead of being a segment of one width each.  Both conditions relax as w grows, so G is
+// non-decreasing in w and a pass is one PIECE of consecutive widths per table entry (bw_sched), run by one instantiation of
+// dmv_bw_segment_p.  At Ne = 41: w 1-8 G = 4, 9-16 G = 8, 17-20 G = 10, 21-24 G = 12, 25-32 G = 16, 33-36 G = 32, 37-40 G = 64.
+// The inside pass keeps make_sched and its power-of-two groups: its butterflies fix the summation tree.
+constexpr int kBwPieces = 7;
+constexpr int bw_group(int k) {
+    constexpr int g[kBwPieces] = {4, 8, 10, 12, 16, 32, 64};
+    return g[k];
+}
+constexpr int bw_waves(int lanes) { return (lanes < VLG_DP_LANES_BW ? lanes : VLG_DP_LANES_BW) / 64; }   // wavefronts per direction that take spans
+constexpr int bw_capacity(int G, int waves) { return waves * (64 / G); }                                  // spans a width may have with groups of G lanes
+// the rule itself: index of the table entry that width w of a sentence of Ne - 1 words runs with
+constexpr int bw_piece_of(int Ne, int w, int waves) {
+    int k = 0;
+    for (int j = 1; j < kBwPieces; ++j)
+        if (Ne - w <= bw_capacity(bw_group(j), waves) && bw_group(j) < 2 * w) k = j;
+    return k;
+}
+struct BwSched {
+    int first[kBwPieces + 1];   // piece k covers first[k] <= w < first[k+1]; first[0] = 1, first[kBwPieces] = Ne
+};
+// the same rule solved for w: first[k] = the smallest width at which entry k (and with it every smaller one) passes both conditions
+constexpr BwSched bw_sched(int Ne, int waves) {
+    BwSched s{};
+    s.first[0] = 1;
+    for (int k = 1; k < kBwPieces; ++k) {
+        const int G = bw_group(k), a = G / 2 + 1, b = Ne - bw_capacity(G, waves);
+        int f = a > b ? a : b;
+        if (f < s.first[k - 1]) f = s.first[k - 1];
+        s.first[k] = f < Ne ? f : Ne;
+    }
+    s.first[kBwPieces] = Ne;
+    return s;
+}
+// the most split points per lane, ceil(w / G), that piece k meets in ANY sentence of N <= n_max: the terms its single body runs
+constexpr int bw_terms(int k, int n_max = kShortN, int waves = bw_waves(VLG_DP_LANES_BW)) {
+    int m = 1;
+    for (int ne = 2; ne <= n_max; ++ne)
+        for (int w = 1; w < ne; ++w) {
+            const int G = bw_group(k), t = (w + G - 1) / G;
+            if (bw_piece_of(ne, w, waves) == k && t > m) m = t;
+        }
+    return m;
+}
+// what dmv_bw_segment_p and the host driver's slack (tests/emu/emu_short.cpp: r < 64) rest on, for every sentence of the short image
+constexpr bool bw_table_ok(int n_max, int waves) {
+    if (waves < 1) return false;
+    for (int k = 0; k < kBwPieces; ++k) {
+        const int G = bw_group(k), TM = bw_terms(k, n_max, waves);
+        if (G < 1 || G > 64 || 64 / G < 1) return false;                    // a group fits a wavefront: at least one per wavefront
+        if (k > 0 && G <= bw_group(k - 1)) return false;                    // ascending: "the largest entry" is the last that passes
+        if (TM > 2 || (G == 64 && TM != 1)) return false;                   // no width needs more than two terms per lane, one at G = 64
+        if (G * TM > 64) return false;                                      // reach of a lane's last term: r = rr + (TM - 1) G < 64
+    }
+    for (int ne = 2; ne <= n_max; ++ne) {
+        const BwSched s = bw_sched(ne, waves);
+        int prev = 0;
+        for (int w = 1; w < ne; ++w) {
+            const int k = bw_piece_of(ne, w, waves);
+            if (ne - w > bw_capacity(bw_group(k), waves)) return false;     // capacity: one span per group and width
+            if (k < prev) return false;                                     // G non-decreasing in w: contiguous pieces
+            if (!(s.first[k] <= w && w < s.first[k + 1])) return false;     // bw_sched is the rule, solved for w
+            prev = k;
+        }
+    }
+    return true;
+}
+static_assert(bw_table_ok(kShortN, bw_waves(VLG_DP_LANES_BW)),
+              "outside-pass group table: capacity, monotone G, at most two terms per lane (one at G = 64), G TM <= 64, a group per wavefront");
+
+// A lane's place in a piece of group size G, from its index t within its direction (dir_lane): wavefront t / 64 holds the GW = 64 / G
+// groups wslot ... wslot + GW - 1, lane l = t % 64 is residue l % G of group l / G, and the lanes l >= GW G are idle -- slot kBwNoSlot,
+// past every span count, so they behave like lanes without a span: they shadow span 0, are never live and never store.  The division
+// by the constant G is taken once per piece.
+constexpr int kBwNoSlot = 0x7fff;
+struct BwLane { int slot, rr, wslot; };
+template <int G>
+VLG_HD BwLane bw_lane(int t) {
+    constexpr int GW = 64 / G;
+    const int l = t & 63, grp = l / G;
+    BwLane b;
+    b.wslot = (t >> 6) * GW;   // the first span of this lane's wavefront
+    b.rr = l - grp * G;
+    b.slot = grp < GW ? b.wslot + grp : kBwNoSlot;
+    return b;
+}
+
 #if defined(__HIPCC__)
 #define VLG_MUL24(a, b) __mul24((a), (b))   // v_mul_i32_i24: full rate (v_mul_lo_u32 is quarter rate); all chart indices < 2^17
 #else
@@ -478,7 +574,7 @@ VLG_HD void dmv_fw_segment(const DmvCtx& c, int w0, int w1, int tid, int nt, X& 
     }
 }
 
-template <int SR, bool BWD, int LG, typename X>
+template <int SR, bool BWD, int LG, int TM = short_tmax(LG, kShortN, VLG_DP_LANES_FW), typename X>
 VLG_HD void dmv_fw_segment_p(const DmvCtx& c, int w0, int w1, int tid, int nt, X& x);   // the short image's form: with the address plans, below
 
 template <int SR, bool BWD, int LONGSPAN, typename X>
@@ -486,8 +582,15 @@ VLG_HD void dmv_fw_all(const DmvCtx& c, int tid, int nt, X& x) {
     const Sched sc = make_sched(c.Ne, nt >> 1, VLG_DP_LANES_FW);
     VLG_WSTAMP(x, 0, 0, 1);   // the pass starts: the "release" before width 1
     if constexpr (LONGSPAN == kSpansShort) {   // the short-sentence image: addresses built per segment and stepped per width (dmv_fw_segment_p)
-        dmv_fw_segment_p<SR, BWD, 0>(c, sc.first[0], sc.first[1], tid, nt, x);
-        dmv_fw_segment_p<SR, BWD, 1>(c, sc.first[1], sc.first[2], tid, nt, x);
+        // Widths 1 and 2 as ONE closed piece of one lane per span and direction (at most kShortN - 1 spans: one wavefront per direction,
+        // no butterfly), the addresses built once: make_sched gives each of them a segment of its own (G = 1, then G = 2 with one term
+        // per lane), and a segment start -- address build, cold code -- is not amortised over one width.  The piece is the G = 1 plan
+        // with its term count following the width: one term at w = 1, two at w = 2 (dmv_fw_dir_p's pieces).  Same bits as the two-lane
+        // group at w = 2: its butterflies are ONE fmaxf and ONE add of the two lanes' terms, both commutative, which is what the
+        // two-term body evaluates in one lane; the term masks, the exponentials, fold_term and first-index-wins (strict > over r = 0, 1
+        // against "smallest lane index that holds the maximum") are the same.
+        static_assert(kShortN - (VLG_DP_LANES_FW >> 2) <= 3, "the short image's segments 0 and 1 are the widths 1 and 2, one each");
+        dmv_fw_segment_p<SR, BWD, 0, 2>(c, sc.first[0], sc.first[2], tid, nt, x);
         dmv_fw_segment_p<SR, BWD, 2>(c, sc.first[2], sc.first[3], tid, nt, x);
         dmv_fw_segment_p<SR, BWD, 3>(c, sc.first[3], sc.first[4], tid, nt, x);
         dmv_fw_segment_p<SR, BWD, 4>(c, sc.first[4], sc.first[5], tid, nt, x);
@@ -857,9 +960,9 @@ VLG_HD void dmv_fw_piece_p(const DmvCtx& c, FwAddr<DIR>& a, int wa, int wb, int 
     }
 }
 
-template <int SR, bool BWD, int DIR, int LG, typename X>
+template <int SR, bool BWD, int DIR, int LG, int TM, typename X>
 VLG_HD void dmv_fw_dir_p(const DmvCtx& c, int w0, int w1, int t, X& x) {
-    constexpr int G = 1 << LG, TM = short_tmax(LG, kShortN, VLG_DP_LANES_FW);
+    constexpr int G = 1 << LG;
     const int rr = t & (G - 1), slot = t >> LG, wslot = (t & ~63) >> LG;   // wslot: the first span of this lane's wavefront
     const int D = slot < c.Ne - w0 ? VLG_MUL24(slot, c.P + 1) : 0;         // no span at any width of the segment: shadow span 0
     FwAddr<DIR> a = dmv_fw_addr<DIR, G, BWD && SR != VLG_SR_MAX>(c, w0, D, rr, x);
@@ -877,15 +980,15 @@ VLG_HD void dmv_fw_dir_p(const DmvCtx& c, int w0, int w1, int t, X& x) {
 }
 
 // all widths of one segment of the short-sentence image
-template <int SR, bool BWD, int LG, typename X>
+template <int SR, bool BWD, int LG, int TM, typename X>
 VLG_HD void dmv_fw_segment_p(const DmvCtx& c, int w0, int w1, int tid, int nt, X& x) {
-    static_assert(short_tmax(LG, kShortN, VLG_DP_LANES_FW) <= 3, "dmv_fw_dir_p's pieces end at three split points per lane");
+    static_assert(TM >= 1 && TM <= 3, "dmv_fw_dir_p's pieces end at three split points per lane");
     if (w1 <= w0) return;
     const int nd = nt >> 1;
     const bool right = x.uniform(tid >= nd);   // taken once per segment: the direction never reaches a width loop
     const int t = dir_lane<VLG_MIRROR_RIGHT>(tid, nd, right);
-    if (right) dmv_fw_dir_p<SR, BWD, 1, LG>(c, w0, w1, t, x);
-    else dmv_fw_dir_p<SR, BWD, 0, LG>(c, w0, w1, t, x);
+    if (right) dmv_fw_dir_p<SR, BWD, 1, LG, TM>(c, w0, w1, t, x);
+    else dmv_fw_dir_p<SR, BWD, 0, LG, TM>(c, w0, w1, t, x);
 }
 
 // the value reads of one width: the own cells and TM terms
@@ -907,7 +1010,7 @@ VLG_HD void dmv_bw_load_vals(const BwAddr& a, BwVals<TM>& v) {
 // One span of width w on the prefetched values `v` (Log semiring: the Max semiring's outside pass is the back-pointer walk), in two
 // halves with the refill of `v` between them (dmv_bw_segment_p).  BwAdj is what the first half hands to the second: the adjoint cells
 // it has requested and the weights' factors.  Both halves run the caller's TM terms at every width: a term past the width's last
-// split point (r >= w; widths 3, 4 of a 40-word sentence have one, and 9 ... 16 had before dmv_bw_all cut their segment in two) reads
+// split point (r >= w; with the group table of round 10 only the widths 1 ... 4 of the G = 4 piece have one) reads
 // cells nobody uses and stores nothing -- its store branch is skipped by the whole wavefront -- where one body per term count T <= TM made the outside pass twice the code, and
 // the bodies' different register assignments met in moves at the loop's end.
 template <int TM>
@@ -975,20 +1078,18 @@ VLG_HD void dmv_bw_span_p2(const BwAddr& a, int w, bool live, bool gc_ok, int rr
     if (live && rr == 0) addr_st(a.aI, 0, gi);   // == d logZ / d attach[j,i,:] | attach[i,j,:]
 }
 
-// widths w1-1 ... w0 of one segment of the short-sentence image (one span per lane group and width: (Ne - w) G <= the lanes of a direction)
-// TM: the terms per lane that the single body runs; the caller may name fewer than the segment's maximum for a run of widths that
-// all have w <= TM G (dmv_bw_all splits the LG = 3 segment so)
-template <int SR, int LG, int TM = short_tmax(LG, kShortN, VLG_DP_LANES_BW), typename X>
+// widths w1-1 ... w0 of one piece of the short-sentence image: groups of G lanes, one span per group and width (bw_capacity), every
+// width with w <= TM G -- the terms per lane that the single body runs (bw_terms)
+template <int SR, int G, int TM, typename X>
 VLG_HD void dmv_bw_segment_p(const DmvCtx& c, int w0, int w1, int tid, int nt, X& x) {
-    constexpr int G = 1 << LG;
-    static_assert(TM >= 1 && TM <= short_tmax(LG, kShortN, VLG_DP_LANES_BW), "more terms than any width of this segment has");
+    static_assert(G >= 1 && G <= 64 && TM >= 1 && G * TM <= 64, "a group sits in one wavefront; a lane's last term stays below split point 64");
     if constexpr (SR == VLG_SR_MAX) return;   // never run: the Max semiring's outside pass is the back-pointer walk (dmv_run)
     if (w1 <= w0) return;
     const int nd = nt >> 1;
     const bool right = x.uniform(tid >= nd);
-    const int t = dir_lane<VLG_MIRROR_RIGHT>(tid, nd, right);
-    const int rr = t & (G - 1), slot = t >> LG, wslot = (t & ~63) >> LG;   // wslot: the first span of this lane's wavefront
-    const int D = slot < c.Ne - w0 ? VLG_MUL24(slot, c.P + 1) : 0;         // no span at any width of the segment: shadow span 0
+    const BwLane ln = bw_lane<G>(dir_lane<VLG_MIRROR_RIGHT>(tid, nd, right));   // (dir_lane permutes whole wavefronts: groups are unchanged)
+    const int rr = ln.rr, slot = ln.slot, wslot = ln.wslot;
+    const int D = slot < c.Ne - w0 ? VLG_MUL24(slot, c.P + 1) : 0;         // no span at any width of the piece (idle lanes too): shadow span 0
     const int gc_hi = right && slot == 0 ? 1 : c.Ne;                       // CR(0, w): zero unless w == len, the width with ONE span (dmv.py:63)
     BwAddr a = dmv_bw_addr<G>(c, w1 - 1, D, rr, right, x);
     // ONE register set of values and ONE place in the loop that refills it, for every wavefront: behind the last use of this width's
@@ -1193,36 +1294,33 @@ VLG_HD void dmv_bw_segment(const DmvCtx& c, int w0, int w1, int tid, int nt, X& 
     }
 }
 
-// (Round 4, measured and not kept: the outside pass has no cross-lane reduction, so its lane groups need not be powers of two --
-//  G = 7 / 10 / 12 between them cut the split points per lane from 3 to 2 for the widths 17 ... 24 and from 2 to 1 for 5 ... 7 at
-//  N = 41, with bit-identical results.  Three more segment instantiations made the launch 1 us SLOWER: each width already runs
-//  code the instruction cache has not seen since the previous launch, and ten segments x two directions x four unrollings is more
-//  of it.  Also measured: the read-modify-writes of the adjoint charts as non-returning ds_add_f32 (one writer per word and phase,
-//  so the same sums): 77 -> 200 us, LDS float atomics are that slow; the four adjoint loads per split point replaced by register
-//  copies (wrong results, an upper bound for interleaving value and adjoint cells): 77.3 -> 74.4 us.)
+// (Lane groups that are no powers of two.  Round 4 measured G = 7 / 10 / 12 in the general dispatch -- every segment four unrolled
+//  bodies per direction -- and dropped them: three more segment instantiations made the launch 1 us slower, the code image again.
+//  Since round 8 a piece of the short image is ONE body of ~150 instructions, and round 10 runs that image's outside pass from the
+//  group table above (bw_group): seven pieces where the powers of two needed nine, two terms per lane at the widths 17 ... 24, and
+//  the kernel is 1.6 KB SMALLER.  The general and long images keep the powers of two.  What the stamps say about the two new
+//  sizes: G = 12 runs a width in ~1 710 cycles where G = 8 with three terms took ~2 060; G = 10 stays at ~2 020, no better than
+//  the three terms it replaces, and why is not established -- the widths 17 ... 20 have no other
+//  size to go to: two terms need G >= 10, 24 spans on four wavefronts need G <= 10.
+//  Also measured in round 4, still not kept: the read-modify-writes of the adjoint charts as non-returning ds_add_f32 (one writer per
+//  word and phase, so the same sums): 77 -> 200 us, LDS float atomics are that slow; the four adjoint loads per split point replaced
+//  by register copies (wrong results, an upper bound for interleaving value and adjoint cells): 77.3 -> 74.4 us.)
 template <int SR, int LONGSPAN = true, typename X>
 VLG_HD void dmv_bw_all(const DmvCtx& c, int tid, int nt, X& x) {
-    const Sched sc = make_sched(c.Ne, nt >> 1, VLG_DP_LANES_BW);
     if constexpr (LONGSPAN == kSpansShort) {   // the short-sentence image: value reads one width ahead (dmv_bw_segment_p)
         VLG_WSTAMP(x, 1, c.Ne, 1);   // the pass starts: the "release" before width Ne - 1
-        dmv_bw_segment_p<SR, 6>(c, sc.first[6], sc.first[7], tid, nt, x);
-        dmv_bw_segment_p<SR, 5>(c, sc.first[5], sc.first[6], tid, nt, x);
-        dmv_bw_segment_p<SR, 4>(c, sc.first[4], sc.first[5], tid, nt, x);
-        {   // LG = 3 is the one segment whose widths differ in their term count by more than the last, partly filled term: 17 ... 24 have
-            // three split points per lane, 9 ... 16 two (T = ceil(w / G) <= TM - 1 <=> w <= (TM - 1) G).  The single-body form runs TM terms
-            // at every width, so it is instantiated twice and the segment cut at that width, high widths first: same stores, same
-            // operands, same order -- the piece with one term fewer only drops a term that stored nothing.
-            constexpr int TM3 = short_tmax(3, kShortN, VLG_DP_LANES_BW), kCut = (TM3 - 1) * (1 << 3) + 1;   // first width that needs TM3 terms
-            static_assert(TM3 >= 2, "a segment of one term per lane has nothing to split off");
-            const int cut = kCut < sc.first[3] ? sc.first[3] : (kCut < sc.first[4] ? kCut : sc.first[4]);
-            dmv_bw_segment_p<SR, 3>(c, cut, sc.first[4], tid, nt, x);
-            dmv_bw_segment_p<SR, 3, TM3 - 1>(c, sc.first[3], cut, tid, nt, x);
-        }
-        dmv_bw_segment_p<SR, 2>(c, sc.first[2], sc.first[3], tid, nt, x);
-        dmv_bw_segment_p<SR, 1>(c, sc.first[1], sc.first[2], tid, nt, x);
-        dmv_bw_segment_p<SR, 0>(c, sc.first[0], sc.first[1], tid, nt, x);
+        const BwSched bs = bw_sched(c.Ne, bw_waves(nt >> 1));   // one piece per entry of the group table, high widths first
+        dmv_bw_segment_p<SR, bw_group(6), bw_terms(6)>(c, bs.first[6], bs.first[7], tid, nt, x);
+        dmv_bw_segment_p<SR, bw_group(5), bw_terms(5)>(c, bs.first[5], bs.first[6], tid, nt, x);
+        dmv_bw_segment_p<SR, bw_group(4), bw_terms(4)>(c, bs.first[4], bs.first[5], tid, nt, x);
+        dmv_bw_segment_p<SR, bw_group(3), bw_terms(3)>(c, bs.first[3], bs.first[4], tid, nt, x);
+        dmv_bw_segment_p<SR, bw_group(2), bw_terms(2)>(c, bs.first[2], bs.first[3], tid, nt, x);
+        dmv_bw_segment_p<SR, bw_group(1), bw_terms(1)>(c, bs.first[1], bs.first[2], tid, nt, x);
+        dmv_bw_segment_p<SR, bw_group(0), bw_terms(0)>(c, bs.first[0], bs.first[1], tid, nt, x);
+        static_assert(kBwPieces == 7, "one call per entry of the group table");
         return;
     }
+    const Sched sc = make_sched(c.Ne, nt >> 1, VLG_DP_LANES_BW);
     if constexpr (LONGSPAN == kSpansLong) {   // long-sentence placements: the value reads as one stream over each segment (dmv_bw_segment_s)
         dmv_bw_segment_s<SR, 6>(c, sc.first[6], sc.first[7], tid, nt, x);
         dmv_bw_segment_s<SR, 5>(c, sc.first[5], sc.first[6], tid, nt, x);
