@@ -112,6 +112,23 @@ int vlg_deptree_sample(const void* arc, const int64_t* lengths, int B, int N, in
                        const float* u, int64_t* heads, float* logp, float* logZ, void* ws, size_t ws_bytes, void* stream);
 int vlg_deptree_sample_blocks(int B, int N, int S);
 
+/* The K best projective single-root trees of every sentence, on the device: `StructDistribution.kmax` / `topk`
+ * (distributions.py:135-156) as scores and head vectors, one launch, 1 <= K <= 16.  One workgroup per sentence fills charts of K
+ * sorted values per cell (k-way merge cells, packed back-pointers r:8 p:4 q:4), then its wavefronts walk one rank each (cell rule,
+ * pruning bound, total order under ties, placement and stack bound: DESIGN.md section 2, "K-best trees").
+ *   scores [K,B] float32, non-increasing in k: the sum, in natural units, of the clamped input potentials along the k-th best tree --
+ *   additions and comparisons only, so exact wherever the partial sums are representable; the scores for K are the first K scores of
+ *   any larger K.  heads [K,B,N] int64 as vlg_deptree_decode writes them (0 for c = 0 and padding): K different trees, also under
+ *   exact ties.  count [B] int32 (optional): the ranks that exist, i.e. whose score is above 0.5 * -1e12; a rank at or beyond count
+ *   (fewer than K trees: a short sentence, forbidden arcs) has score -1e12 exactly and heads 0.  lengths is optional (NULL: N - 1).
+ *   An invalid length gives count 0, heads 0 and scores NaN.
+ *   ws holds vlg_deptree_kbest_workspace(B, N, K) bytes (0 where the charts fit in LDS; 0 for arguments out of range).
+ *   VLG_ERR_SHAPE for N outside 2 ... 255 or K outside 1 ... 16, VLG_ERR_DTYPE, VLG_ERR_NULL for NULL arc / heads / scores,
+ *   VLG_ERR_WORKSPACE; B = 0 is a no-op. */
+int vlg_deptree_kbest(const void* arc, const int64_t* lengths, int B, int N, int in_dtype, int K, int64_t* heads, float* scores,
+                      int32_t* count, void* ws, size_t ws_bytes, void* stream);
+size_t vlg_deptree_kbest_workspace(int B, int N, int K);
+
 /* Expectations under the projective CRF, on the device: the DepTree inside(-outside) pass in dual numbers, one launch.  Every chart
  * cell carries its derivative along the direction d = v - v_sub in potential space (rule: DESIGN.md section 2, "Expectations").
  *   arc [B,N,N] in in_dtype; v, v_sub [B,N,N] in v_dtype (VLG_F32 / VLG_BF16), each optional: NULL reads as 0.  d is forced to 0 where

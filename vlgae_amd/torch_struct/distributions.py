@@ -21,7 +21,7 @@ def _out_of_scope(name):
         f"StructDistribution.{name}: no caller in VLGAE uses it (only partition / max / argmax / marginals are "
         "reached; SURVEY.md section 2) -- outside the MI355X hot path this package implements.  (Drawing trees is "
         "implemented for DependencyCRF as `sample_heads` / `heads_to_parts`; entropy, cross-entropy, KL and expected scores as "
-        "`tree_entropy` / `tree_cross_entropy` / `tree_kl` / `expected_score`.)")
+        "`tree_entropy` / `tree_cross_entropy` / `tree_kl` / `expected_score`; the k best trees as `kbest_heads` / `kbest_scores`.)")
 
 
 class StructDistribution(Distribution):
@@ -237,6 +237,21 @@ class DependencyCRF(StructDistribution):
         if own:
             rng.advance()
         return (heads, logp) if return_log_prob else heads
+
+    # -- k-best trees (extension: one launch, functional.deptree_kbest).  The reference's `kmax(k)` / `topk(k)` (distributions.py:135-156)
+    # stay out of scope under those names, as `sample` does next to `sample_heads`.
+    def kbest_heads(self, k, return_scores=False):
+        """The k best trees (1 <= k <= 16) as heads [k,B,N] int64 on the device: k different trees per sentence, also under exact
+        ties, best first; `DependencyCRF.heads_to_parts(dist.kbest_heads(k), lengths)` is the event format of the reference's
+        `topk(k)`.  return_scores=True: (heads, scores [k,B] float32, count [B] int32) -- a sentence with fewer than k trees has
+        count < k, and its ranks at or beyond count hold score NEGINF and heads 0."""
+        heads, scores, count = F.deptree_kbest(self.log_potentials, self.lengths, k)
+        return (heads, scores, count) if return_scores else heads
+
+    def kbest_scores(self, k):
+        """Scores [k,B] of the k best trees, non-increasing in k: the reference's `kmax(k)` wherever the rank exists (NEGINF where it
+        does not).  Differentiable once with respect to the potentials: the gradient of scores[k,b] is tree (k,b)'s arc indicators."""
+        return F.deptree_kbest_scores(self.log_potentials, self.lengths, k)[0]
 
     # -- expectations (extension: one dual-number inside-outside launch each, exact gradients; functional.deptree_expect) ------------
     # The reference's names (`entropy`, `cross_entropy`, `kl`, `risk`, distributions.py:79-114) stay out of scope under those names,

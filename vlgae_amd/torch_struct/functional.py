@@ -257,6 +257,66 @@ def deptree_sample(arc, lengths, n, rng=None, site=0, u=None, want_logp=True):
     return heads, logp, logZ
 
 
+_KBEST_WS_BYTES = {}
+
+
+def deptree_kbest(arc, lengths, k):
+    """The k best projective single-root trees of arc scores [B,N,N], 1 <= k <= 16, in ONE launch (vlg_deptree_kbest):
+    (heads [k,B,N] int64 as deptree_decode writes them, scores [k,B] float32 non-increasing in k, count [B] int32).  A rank at or
+    beyond count[b] does not exist (short sentence, forbidden arcs): score NEGINF, heads 0.  No host synchronisation."""
+    _C.require_gpu(arc, "deptree_kbest")
+    if arc.dim() != 3:
+        raise ValueError("potentials must have dim of 3 (unlabeled)")
+    B, N, N2 = arc.shape
+    assert N == N2, "Non-square potentials"
+    k = int(k)
+    dt, arc_c = _C.in_dtype(arc)
+    lengths = _lengths(lengths, B, arc.device, allow_none=True)
+    heads = torch.empty((k, B, N), dtype=torch.int64, device=arc.device)
+    scores = torch.empty((k, B), dtype=torch.float32, device=arc.device)
+    count = torch.empty(B, dtype=torch.int32, device=arc.device)
+    L = _C.lib()
+    nb = _KBEST_WS_BYTES.get((B, N, k))
+    if nb is None:
+        nb = _KBEST_WS_BYTES[(B, N, k)] = L.vlg_deptree_kbest_workspace(B, N, k)
+    ws = torch.empty(nb, dtype=torch.uint8, device=arc.device) if nb else None
+    _C.check(L.vlg_deptree_kbest(_C.ptr(arc_c), _C.ptr(lengths), B, N, dt, k, _C.ptr(heads), _C.ptr(scores), _C.ptr(count), _C.ptr(ws), nb,
+                                 _C.stream_of(arc)), "deptree_kbest")
+    return heads, scores, count
+
+
+class _DepTreeKBestScores(torch.autograd.Function):
+    """scores [k,B] of the k best trees; d scores[k,b] / d arc[b,h,c] = 1 on the arcs of tree (k,b), for the ranks that exist."""
+
+    @staticmethod
+    def forward(ctx, arc, lengths, k):
+        heads, scores, count = deptree_kbest(arc.detach(), lengths, k)
+        ctx.save_for_backward(heads, count)
+        ctx.arc_shape, ctx.arc_dtype, ctx.lengths = arc.shape, arc.dtype, lengths
+        ctx.mark_non_differentiable(heads, count)
+        return scores, heads, count
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_scores, _gh, _gc):
+        heads, count = ctx.saved_tensors
+        K, B, N = heads.shape
+        pos = torch.arange(N, device=heads.device)
+        ln = pos.new_full((B,), N - 1) if ctx.lengths is None else torch.as_tensor(ctx.lengths, device=heads.device).to(torch.int64)
+        word = (pos >= 1) & (pos <= ln.unsqueeze(-1))                                             # [B,N]
+        live = torch.arange(K, device=heads.device).unsqueeze(-1) < count.unsqueeze(0)            # [K,B]
+        w = grad_scores.to(torch.float32).unsqueeze(-1) * (word.unsqueeze(0) & live.unsqueeze(-1))   # [K,B,N]: grad[k,b] at every word of a live rank
+        garc = torch.zeros((B, N, N), dtype=torch.float32, device=heads.device)
+        b_idx = torch.arange(B, device=heads.device).view(1, B, 1).expand(K, B, N)
+        garc.index_put_((b_idx, heads, pos.view(1, 1, N).expand(K, B, N)), w, accumulate=True)    # += grad[k,b] at [b, heads[k,b,c], c]
+        return garc.to(ctx.arc_dtype), None, None
+
+
+def deptree_kbest_scores(arc, lengths, k):
+    "(scores [k,B] differentiable once in arc, heads [k,B,N], count [B])"
+    return _DepTreeKBestScores.apply(arc, lengths, k)
+
+
 def deptree_mbr_decode(marginals, lengths=None):
     """The MBR decode of src/model/ldndmv.py:294-299 from the DMV1o arc marginals [B,N,N,2] (float32: `grad_attach` of the Log
     semiring's inside-outside pass): `DependencyCRF(marginals.sum(-1)).argmax` as (best_score [B], heads [B,N] int64) in ONE DepTree
