@@ -760,6 +760,22 @@ VLG_HD void dmv_bw_span(const DmvCtx& c, int w, int G, int D, bool live, int rr,
 // A lane that has no span at any width of the segment shadows span 0; one that gets its span later in the segment addresses it from
 // the start, so until then its (unused) reads fall on rows past Ne: inside twice the chart's cells, never stored through.  Like the
 // out-of-range split points of NOCLAMP, they need memory that can be read: LDS on the device, the arena plus slack in the host driver.
+//
+// Stationary cells (round 11).  The xa row of the table has stride [0] in both directions: over a piece a lane's term u reads the same
+// value cell CR(i, i + r), r = rr + u G, and adds to the same adjoint word -- component .NC of gCi[CR(i, i + r)] from the left
+// direction, .HC from the right -- at every width w > r.  dmv_bw_segment_p reads the value once, at the piece's start (the refill
+// leaves it out), and keeps the adjoint word in a register: loaded at the piece's start, the width's weight added to it where the
+// parent added it to the word just read, the sum stored where the parent stored it.  Same addends in the same order; the chart holds
+// the current sum behind every width, so every reader finds what it found before -- what is gone are T value reads and T adjoint
+// reads per width.  Single owner, per word: the only stores to component c of gCi at a cell right of the diagonal, (row i, column
+// i + r + 1), are the xa stores of direction c's spans (i, i + w), w > r, at split point r (xb stores fall on cells (row j, column
+// <= j), on or left of the diagonal; the own cells of gCi are only read).  Those spans differ in w alone, and within a piece slot i,
+// residue rr and term u belong to ONE lane at every width -- so from the piece's start to its end nobody else stores to the word the
+// lane holds, also while the lane is not live yet (its span begins at a lower width of the piece: it has loaded the word of its own
+// row i, which the lanes of other rows never address).  The next piece deals the word to another lane, which loads it behind this
+// piece's last barrier.  tests/emu/plan_short.cpp replays the pass on counters and checks exactly this for every N, Ne, piece and lane.
+// (Storing the word only with its last contribution, r == w - 1, and at the piece's last width -- a nested, lane-dependent branch per
+// term -- made a two-term width body 167 instructions where this form has 138 and the parent 140: DESIGN.md section 7.)
 template <int TM>
 struct BwVals {
     float2 oc, sv, vv[TM];
@@ -992,7 +1008,7 @@ VLG_HD void dmv_fw_segment_p(const DmvCtx& c, int w0, int w1, int tid, int nt, X
 }
 
 // the value reads of one width: the own cells and TM terms
-template <int G, int TM>
+template <int G, int TM, bool XA = true>
 VLG_HD void dmv_bw_load_vals(const BwAddr& a, BwVals<TM>& v) {
     v.oc = addr_ld<float2>(a.vC);
     v.Sv = addr_ld<float>(a.vS);
@@ -1002,7 +1018,7 @@ VLG_HD void dmv_bw_load_vals(const BwAddr& a, BwVals<TM>& v) {
     for (int u = 0; u < TM; ++u) {
         v.uu[u] = addr_ld<float>(a.vUU, u * a.gp8);
         v.vv[u] = addr_ld<float2>(a.vVV, u * G * 8);
-        v.xa[u] = addr_ld<float>(a.vXA, u * G * 8);
+        if constexpr (XA) v.xa[u] = addr_ld<float>(a.vXA, u * G * 8);   // stationary: read at the piece's start only
         v.xb[u] = addr_ld<float>(a.vXB, u * G * 8);
     }
 }
@@ -1015,7 +1031,7 @@ VLG_HD void dmv_bw_load_vals(const BwAddr& a, BwVals<TM>& v) {
 // the bodies' different register assignments met in moves at the loop's end.
 template <int TM>
 struct BwAdj {
-    float ga, o_c[TM], o_ga[TM], o_gb[TM];
+    float ga, o_c[TM], o_gb[TM];
     float2 gb, gi_old, o_gi[TM];
     float e0[TM], e1[TM], es[TM], s0, s1;   // factors 2^min(t - out, 0) of the terms of CL | CR (.x, .y) and SL | SR, and of the same-width term
 };
@@ -1031,7 +1047,6 @@ VLG_HD void dmv_bw_span_p1(const BwAddr& a, X& x, const BwVals<TM>& v, BwAdj<TM>
     for (int u = 0; u < TM; ++u) {
         s.o_gi[u] = addr_ld<float2>(a.aVV, u * G * 8);
         s.o_c[u] = addr_ld<float>(a.aUU, u * a.gp4);
-        s.o_ga[u] = addr_ld<float>(a.aXA, u * G * 8);
         s.o_gb[u] = addr_ld<float>(a.aXB, u * G * 8);
     }
 #pragma unroll
@@ -1057,7 +1072,7 @@ VLG_HD void dmv_bw_span_p1(const BwAddr& a, X& x, const BwVals<TM>& v, BwAdj<TM>
 // second half: the weights and the read-modify-writes.  gc_ok: the span is live and not the masked root cell; selfr: the split point
 // whose incomplete span has this same width.
 template <int G, int TM, typename X>
-VLG_HD void dmv_bw_span_p2(const BwAddr& a, int w, bool live, bool gc_ok, int rr, int selfr, X& x, const BwAdj<TM>& s) {
+VLG_HD void dmv_bw_span_p2(const BwAddr& a, int w, bool live, bool gc_ok, int rr, int selfr, X& x, const BwAdj<TM>& s, float (&gxa)[TM]) {
     float2 gc = make_float2(0.f, 0.f);                        // total adjoint of CL(j,i) | CR(i,j)
     if (gc_ok) gc = make_float2(s.gb.x, s.ga + s.gb.y);       // (zero for a dead lane and for the masked root cell, dmv.py:63)
     const float self0 = gc.x * s.s0, self1 = gc.y * s.s1;
@@ -1071,7 +1086,8 @@ VLG_HD void dmv_bw_span_p2(const BwAddr& a, int w, bool live, bool gc_ok, int rr
             const float w0 = gc.x * s.e0[u], w1 = gc.y * s.e1[u], ws = gs * s.es[u];
             if (r != selfr) addr_st(a.aVV, u * G * 8, make_float2(s.o_gi[u].x + w0, s.o_gi[u].y + w1));
             addr_st(a.aUU, u * a.gp4, s.o_c[u] + (w0 + w1));
-            addr_st(a.aXA, u * G * 8, s.o_ga[u] + ws);
+            gxa[u] += ws;   // the stationary word of xa: summed in its register (the same addends in the same order), written through
+            addr_st(a.aXA, u * G * 8, gxa[u]);
             addr_st(a.aXB, u * G * 8, s.o_gb[u] + ws);
         }
     }
@@ -1099,14 +1115,19 @@ VLG_HD void dmv_bw_segment_p(const DmvCtx& c, int w0, int w1, int tid, int nt, X
     BwVals<TM> v;
     dmv_bw_load_vals<G, TM>(a, v);
     a.step_vals();
+    // the stationary cells of the piece (the table above BwAddr, stride [0] in both directions): xa stays in `v` -- the refill leaves it
+    // out -- and its adjoint word is held in gxa from here to the piece's end, written through with every contribution
+    float gxa[TM];
+#pragma unroll
+    for (int u = 0; u < TM; ++u) gxa[u] = addr_ld<float>(a.aXA, u * G * 8);
     for (int w = w1 - 1; w >= w0; --w) {
         const int spans = x.uniform(c.Ne - w), selfr = x.uniform(right ? w - 1 : 0);   // (pinned to scalar registers, and the loop counter with them)
         const bool live = slot < spans;
         const bool body = !(X::kSkipDeadWaves && wslot >= spans);   // (wave-uniform) a wavefront without a span of this width: only the refill
         BwAdj<TM> s;
         if (body) dmv_bw_span_p1<G, TM>(a, x, v, s);
-        dmv_bw_load_vals<G, TM>(a, v);
-        if (body) dmv_bw_span_p2<G, TM>(a, w, live, live && spans <= gc_hi, rr, selfr, x, s);
+        dmv_bw_load_vals<G, TM, false>(a, v);
+        if (body) dmv_bw_span_p2<G, TM>(a, w, live, live && spans <= gc_hi, rr, selfr, x, s, gxa);
         a.step_vals();
         a.step_adj();
         VLG_WSTAMP(x, 1, w, 0);
