@@ -205,7 +205,10 @@ int vlg_bilinear_align(const void* txt, const void* vis, const uint8_t* tmask, c
  * terms (g = t0 + t1, dropping < 2^-17 |g|), bf16 features are used as they are, fp32 features as two bf16 parts (x = hi + lo;
  * the lo x t1 product, < 2^-16 of the term, is dropped), against contraction-major copies of the features that live in `ws`:
  * vlg_bilinear_align_backward_workspace(...) bytes of device scratch (0 when the fast path does not apply; ws may then be NULL).
- * Other shapes: fp32 matrix-core products, exact. */
+ * Other shapes: fp32 matrix-core products, exact.
+ * grad_out must be finite everywhere, masked positions included: the kernels remove the contraction-side terms of a mask, and the
+ * positions they over-read past a short contraction, by multiplying with features staged as zeros, so an Inf or NaN there would
+ * reach the sums (a finite value of any size does not). */
 size_t vlg_bilinear_align_backward_workspace(int B, int A, int Q, int V, int d, int in_dtype);
 int vlg_bilinear_align_backward(const float* grad_out, const void* txt, const void* vis, const uint8_t* tmask, const uint8_t* vmask,
                                 int B, int A, int Q, int V, int d, int in_dtype, void* ws, size_t ws_bytes, float* grad_txt,
