@@ -112,6 +112,25 @@ int vlg_deptree_sample(const void* arc, const int64_t* lengths, int B, int N, in
                        const float* u, int64_t* heads, float* logp, float* logZ, void* ws, size_t ws_bytes, void* stream);
 int vlg_deptree_sample_blocks(int B, int N, int S);
 
+/* The same for the DMV with valence: S trees per sentence from DMV1o's distribution, one launch.  The Log-semiring inside pass of
+ * vlg_dmv1o_inside runs once per workgroup (same chart placement); then every wavefront walks whole samples top-down from
+ * CR(0,len).NOCHILD, every cell carrying its valence (rule table, keys and LDS budget: DESIGN.md section 2, "Drawing DMV1o trees").
+ *   dec [B,N,2,2,2] / attach [B,N,N,2] root-merged, in in_dtype; lengths [B] is required.  rng / site / u exactly as for
+ *   vlg_deptree_sample: the key of a draw is (kind, lo, hi) of the span -- no valence, no direction -- under sample s and sentence b.
+ *   heads [S,B,N] int64; logp [S,B] (optional) = the tree's score on the input potentials (attach + dec GO per arc, dec STOP per
+ *   head, side and valence) - logZ; logZ [B] (optional).  An invalid length gives heads 0, logp NaN, logZ NaN.
+ *   The launch is a (B, Y) grid, Y = vlg_dmv1o_sample_blocks(B, N, S); ws holds vlg_dmv1o_sample_workspace(B, N, S) bytes (Y included;
+ *   0 where the charts fit in LDS, and for arguments out of range); vlg_dmv1o_sample_lds_bytes(N) is the dynamic LDS of one workgroup,
+ *   the wavefronts' stacks included (0 for N out of range).
+ *   VLG_ERR_NULL unless exactly one of rng / u is non-NULL, and for NULL dec / attach / lengths / heads; VLG_ERR_SHAPE for N outside
+ *   2 ... 255 or S < 1; VLG_ERR_DTYPE; VLG_ERR_WORKSPACE; B = 0 is a no-op. */
+int vlg_dmv1o_sample(const void* dec, const void* attach, const int64_t* lengths, int B, int N, int in_dtype, int S,
+                     const uint64_t* rng, unsigned site, const float* u, int64_t* heads, float* logp, float* logZ, void* ws,
+                     size_t ws_bytes, void* stream);
+int vlg_dmv1o_sample_blocks(int B, int N, int S);
+size_t vlg_dmv1o_sample_workspace(int B, int N, int S);
+size_t vlg_dmv1o_sample_lds_bytes(int N);
+
 /* The K best projective single-root trees of every sentence, on the device: `StructDistribution.kmax` / `topk`
  * (distributions.py:135-156) as scores and head vectors, one launch, 1 <= K <= 16.  One workgroup per sentence fills charts of K
  * sorted values per cell (k-way merge cells, packed back-pointers r:8 p:4 q:4), then its wavefronts walk one rank each (cell rule,

@@ -1,6 +1,7 @@
 """Register / scratch / LDS figures of every kernel in the built objects, from the gfx950 code-object notes.
 
     python tools/codeobj.py [pattern]     # kernels whose demangled name contains the pattern
+    python tools/codeobj.py --digest [DIR]   # sha256 of every object's gfx950 code object (DIR: another build's objects), to compare builds
 
 For each translation-unit object in vlgae_amd/_lib the gfx950 offload bundle is extracted (llvm-objdump --offloading, in a
 temporary directory) and its AMDGPU metadata note (YAML) parsed: vgpr_count, agpr_count, spills, private segment (scratch)
@@ -58,7 +59,27 @@ def all_kernels():
     return res
 
 
+def digests(lib_dir=None):
+    """{object name: [sha256 of each gfx950 code object in it]} for a directory of objects built by vlgae_amd.build: two builds whose
+    digests agree run the same device code (`python tools/codeobj.py --digest [DIR]`, once per build, and compare the lines)."""
+    import hashlib
+    res = {}
+    for obj in sorted(glob.glob(os.path.join(lib_dir or os.path.join(ROOT, "vlgae_amd", "_lib"), "*.o"))):
+        with tempfile.TemporaryDirectory() as td:
+            local = os.path.join(td, os.path.basename(obj))
+            shutil.copy(obj, local)
+            subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", local], cwd=td, stdout=subprocess.DEVNULL,
+                           stderr=subprocess.DEVNULL)
+            res[os.path.basename(obj)] = [hashlib.sha256(open(co, "rb").read()).hexdigest() for co in sorted(glob.glob(os.path.join(td, "*gfx950*")))]
+    return res
+
+
 if __name__ == "__main__":
+    if "--digest" in sys.argv:
+        rest = [a for a in sys.argv[1:] if a != "--digest"]
+        for name, shas in digests(rest[0] if rest else None).items():
+            print(name, *shas)
+        sys.exit(0)
     pat = sys.argv[1] if len(sys.argv) > 1 else ""
     for k in all_kernels():
         if pat in k.get("demangled", ""):

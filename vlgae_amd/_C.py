@@ -64,6 +64,10 @@ SIGNATURES = {
     "vlg_deptree_mbr_decode": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "vlg_deptree_sample": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, ctypes.c_uint, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vlg_deptree_sample_blocks": (_i, [_i, _i, _i]),
+    "vlg_dmv1o_sample": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, ctypes.c_uint, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "vlg_dmv1o_sample_blocks": (_i, [_i, _i, _i]),
+    "vlg_dmv1o_sample_workspace": (_sz, [_i, _i, _i]),
+    "vlg_dmv1o_sample_lds_bytes": (_sz, [_i]),
     "vlg_deptree_kbest": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vlg_deptree_kbest_workspace": (_sz, [_i, _i, _i]),
     "vlg_deptree_expect": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

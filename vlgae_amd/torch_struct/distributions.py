@@ -20,7 +20,7 @@ def _out_of_scope(name):
     raise NotImplementedError(
         f"StructDistribution.{name}: no caller in VLGAE uses it (only partition / max / argmax / marginals are "
         "reached; SURVEY.md section 2) -- outside the MI355X hot path this package implements.  (Drawing trees is "
-        "implemented for DependencyCRF as `sample_heads` / `heads_to_parts`; entropy, cross-entropy, KL and expected scores as "
+        "implemented for DependencyCRF as `sample_heads` / `heads_to_parts` and for DMV1o as `sample_heads` / `log_prob_heads`; entropy, cross-entropy, KL and expected scores as "
         "`tree_entropy` / `tree_cross_entropy` / `tree_kl` / `expected_score`; the k best trees as `kbest_heads` / `kbest_scores`.)")
 
 
@@ -149,6 +149,32 @@ class DMV1o(StructDistribution):
         heads) joins them into the current stream.  Work enqueued in between overlaps the DPs (functional.dmv1o_structure_async)."""
         dec, attach = self.log_potentials
         return F.dmv1o_structure_async(dec, attach, self.lengths, keep_viterbi)
+
+    def sample_heads(self, n, rng=None, u=None, return_log_prob=False):
+        """Extension (not in the reference): n trees per sentence drawn from the distribution, as heads [n,B,N] int64 on the device
+        (heads[s,b,c] = head of word c, 0 for c = 0 and padding) -- one kernel launch, no host synchronisation.  The semantics of
+        `DependencyCRF.sample_heads`: `rng` an `encoders.DeviceRng` whose (seed, step) keys the draws (the caller advances it), `u`
+        explicit uniforms [n,B,3,N,N] instead; with neither, the distribution creates and keeps a DeviceRng seeded from
+        `torch.initial_seed()` and advances it after each call.  return_log_prob=True: (heads, log_prob [n,B]).  The reference's
+        `sample(sample_shape)` (distributions.py:195-217) stays out of scope under that name."""
+        dec, attach = self.log_potentials
+        own = rng is None and u is None
+        if own:
+            if getattr(self, "_sample_rng", None) is None:
+                from ..encoders import DeviceRng
+                self._sample_rng = DeviceRng(torch.initial_seed() & 0x7FFFFFFFFFFFFFFF, dec.device)
+            rng = self._sample_rng
+        heads, logp, _ = F.dmv1o_sample(dec, attach, self.lengths, n, rng=rng, u=u, want_logp=return_log_prob)
+        if own:
+            rng.advance()
+        return (heads, logp) if return_log_prob else heads
+
+    def log_prob_heads(self, heads):
+        """Extension: log p(tree) for head vectors [..., B, N] -> [..., B]: the tree's score (every attachment with its valence and GO
+        decision, every STOP) minus `partition`.  Differentiable once with respect to both potentials: the gradient is the tree's
+        counts minus the expected counts -- the score-function estimator's term for trees drawn by `sample_heads`."""
+        dec, attach = self.log_potentials
+        return F.dmv1o_log_prob_heads(dec, attach, self.lengths, heads)
 
     @staticmethod
     def merge(dec: Tensor, attach: Tensor, root: Tensor, one=0, zero=NEGINF):

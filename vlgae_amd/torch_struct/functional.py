@@ -257,6 +257,79 @@ def deptree_sample(arc, lengths, n, rng=None, site=0, u=None, want_logp=True):
     return heads, logp, logZ
 
 
+def dmv1o_sample(dec, attach, lengths, n, rng=None, site=0, u=None, want_logp=True):
+    """n trees per sentence drawn from the DMV of root-merged potentials dec [B,N,2,2,2] / attach [B,N,N,2], in ONE launch
+    (vlg_dmv1o_sample): (heads [n,B,N] int64 as dmv1o_decode writes them, logp [n,B] float32 or None, logZ [B]).  The uniforms come
+    either from `rng` (an encoders.DeviceRng, `site` as for the dropout layers) or from the explicit table `u` [n,B,3,N,N] float32,
+    read at [s,b,kind,lo,hi]; exactly one of the two -- the semantics of deptree_sample."""
+    _C.require_gpu(dec, "dmv1o_sample")
+    if dec.dim() != 5 or tuple(dec.shape[2:]) != (2, 2, 2):
+        raise ValueError(f"dec must be [B,N,2,2,2], got {tuple(dec.shape)}")
+    B, N = dec.shape[:2]
+    if tuple(attach.shape) != (B, N, N, 2):
+        raise ValueError(f"attach must be [B,N,N,2] = {(B, N, N, 2)}, got {tuple(attach.shape)}")
+    n = int(n)
+    if dec.dtype != attach.dtype:
+        attach = attach.to(dec.dtype)
+    dt, dec_c = _C.in_dtype(dec)
+    _, att_c = _C.in_dtype(attach)
+    lengths = _lengths(lengths, B, dec.device)
+    if (rng is None) == (u is None):
+        raise ValueError("dmv1o_sample: pass exactly one of rng and u")
+    if u is not None:
+        if tuple(u.shape) != (n, B, 3, N, N) or u.dtype != torch.float32 or u.device != dec.device:
+            raise ValueError(f"dmv1o_sample: u must be float32 [n,B,3,N,N] = {(n, B, 3, N, N)} on {dec.device}")
+        u = u.contiguous()
+    heads = torch.empty((n, B, N), dtype=torch.int64, device=dec.device)
+    logp = torch.empty((n, B), dtype=torch.float32, device=dec.device) if want_logp else None
+    logZ = torch.empty(B, dtype=torch.float32, device=dec.device)
+    L = _C.lib()
+    nb = L.vlg_dmv1o_sample_workspace(B, N, n)
+    ws = torch.empty(nb, dtype=torch.uint8, device=dec.device) if nb else None
+    _C.check(L.vlg_dmv1o_sample(_C.ptr(dec_c), _C.ptr(att_c), _C.ptr(lengths), B, N, dt, n, None if rng is None else _C.ptr(rng.state),
+                                int(site), _C.ptr(u), _C.ptr(heads), _C.ptr(logp), _C.ptr(logZ), _C.ptr(ws), nb, _C.stream_of(dec)),
+             "dmv1o_sample")
+    return heads, logp, logZ
+
+
+def dmv1o_tree_score(md, ma, heads, lengths, big=1e4):
+    """Score of the dependency tree `heads` [B,N] (heads[b,c] = head of word c, 0 = the root token) under root-merged DMV1o potentials
+    md [B,N,2,2,2] / ma [B,N,N,2 (head, child, valence)]: [B,1], differentiable w.r.t. both (its gradient is the tree's derivation
+    counts).  The counts come from the Max-semiring DP itself on potentials whose arcs (heads[c] -> c) carry a bonus that no other tree
+    can make up: the valence of every attachment and every continue / stop decision are functions of the tree, so the arg-max derivation
+    of the biased potentials IS the derivation of that tree, under exactly the conventions the kernel uses."""
+    from .distributions import DMV1o
+    B, N = heads.shape
+    with torch.no_grad():
+        child = torch.arange(N, device=heads.device)[None].expand(B, -1)
+        live = (child >= 1) & (child <= lengths[:, None])
+        bonus = torch.zeros((B, N, N), dtype=torch.float32, device=heads.device)
+        b_idx = torch.arange(B, device=heads.device)[:, None].expand(-1, N)
+        bonus[b_idx[live], heads[live], child[live]] = big
+    with torch.enable_grad():
+        pot = [md.detach().float().requires_grad_(True), (ma.detach().float() + bonus.unsqueeze(-1)).requires_grad_(True)]
+        cd, ca = torch.autograd.grad(DMV1o(pot, lengths).max.sum(), pot)
+    ct = torch.float64 if md.dtype == torch.float64 else torch.float32   # (the tests' float64 formulation keeps its precision)
+    return ((cd.to(ct) * md.to(ct)).flatten(1).sum(1) + (ca.to(ct) * ma.to(ct)).flatten(1).sum(1)).view(B, 1)
+
+
+def dmv1o_log_prob_heads(dec, attach, lengths, heads):
+    """log p(tree) of head vectors [..., B, N] under the DMV of root-merged potentials: [..., B], the tree's score (dmv1o_tree_score)
+    minus the log-partition.  Differentiable once w.r.t. both potentials: the tree's counts minus the expected counts.  Leading
+    dimensions fold into the batch (the potentials are repeated for the score's Max-semiring launch; the partition is taken once)."""
+    B, N = dec.shape[:2]
+    if heads.shape[-2:] != (B, N):
+        raise ValueError(f"heads must be [..., B, N] = [..., {B}, {N}], got {tuple(heads.shape)}")
+    lead = heads.shape[:-2]
+    k = 1
+    for d in lead:
+        k *= int(d)
+    lengths = _lengths(lengths, B, dec.device)
+    rep = lambda t: t.unsqueeze(0).expand((k,) + tuple(t.shape)).reshape((k * B,) + tuple(t.shape[1:]))
+    score = dmv1o_tree_score(rep(dec), rep(attach), heads.reshape(k * B, N), rep(lengths)).view(lead + (B,))
+    return score - dmv1o_sum(dec, attach, lengths, _C.SEMIRING_LOG).reshape(B).to(score.dtype)
+
+
 _KBEST_WS_BYTES = {}
 
 

@@ -120,24 +120,10 @@ def scorer_feed_forward(P, emb, x_fused, drop_head=None, drop_small=None, drop_m
 
 
 def forced_tree_score(md, ma, heads, lengths, big=1e4):
-    """Score of the dependency tree `heads` [B,N] (heads[b,c] = head of word c, 0 = the root token) under root-merged DMV1o potentials
-    md [B,N,2,2,2] / ma [B,N,N,2 (head, child, valence)]: [B,1], differentiable w.r.t. both (its gradient is the tree's derivation
-    counts).  The counts come from the Max-semiring DP itself on potentials whose arcs (heads[c] -> c) carry a bonus that no other tree
-    can make up: the valence of every attachment and every continue / stop decision are functions of the tree, so the arg-max derivation
-    of the biased potentials IS the derivation of that tree, under exactly the conventions the kernel uses."""
-    import vlgae_amd.torch_struct as ts
-    B, N = heads.shape
-    with torch.no_grad():
-        child = torch.arange(N, device=heads.device)[None].expand(B, -1)
-        live = (child >= 1) & (child <= lengths[:, None])
-        bonus = torch.zeros((B, N, N), dtype=torch.float32, device=heads.device)
-        b_idx = torch.arange(B, device=heads.device)[:, None].expand(-1, N)
-        bonus[b_idx[live], heads[live], child[live]] = big
-    with torch.enable_grad():
-        pot = [md.detach().float().requires_grad_(True), (ma.detach().float() + bonus.unsqueeze(-1)).requires_grad_(True)]
-        cd, ca = torch.autograd.grad(ts.DMV1o(pot, lengths).max.sum(), pot)
-    ct = torch.float64 if md.dtype == torch.float64 else torch.float32   # (the tests' float64 formulation keeps its precision)
-    return ((cd.to(ct) * md.to(ct)).flatten(1).sum(1) + (ca.to(ct) * ma.to(ct)).flatten(1).sum(1)).view(B, 1)
+    """Score [B,1] of the dependency tree `heads` [B,N] under root-merged DMV1o potentials, differentiable w.r.t. both: the body lives in
+    vlgae_amd.torch_struct.functional.dmv1o_tree_score (DMV1o.log_prob_heads shares it)."""
+    from vlgae_amd.torch_struct.functional import dmv1o_tree_score
+    return dmv1o_tree_score(md, ma, heads, lengths, big)
 
 
 # ----------------------------------------------------------------------------------------------------------------------------
