@@ -164,6 +164,23 @@ size_t vlg_deptree_kbest_workspace(int B, int N, int K);
 int vlg_deptree_expect(const void* arc, const void* v, const void* v_sub, const int64_t* lengths, int B, int N, int in_dtype, int v_dtype,
                        float* logZ, float* ev, float* mu, float* hv, void* ws, size_t ws_bytes, void* stream);
 
+/* The same for the valence DMV (DMV1o): its inside(-outside) pass in dual numbers, one launch (rule: DESIGN.md section 2,
+ * "Expectations under DMV1o").  The direction is d = (v_dec - v_sub_dec, v_attach - v_sub_attach).
+ *   dec [B,N,2,2,2], attach [B,N,N,2] root-merged potentials in in_dtype; lengths [B] int64.  v_dec, v_sub_dec are dec-shaped and
+ *   v_attach, v_sub_attach attach-shaped, in v_dtype (VLG_F32 / VLG_BF16); each is optional and NULL reads as 0.  A component of d is
+ *   forced to 0 where its own potential is forbidden (at or below the semiring zero vlg_dmv1o_merge writes, -inf included) and outside
+ *   the sentence; elsewhere it must be finite.
+ *   logZ [B] (required); ev [B] = <mu, d>; mu_dec [B,N,2,2,2], mu_attach [B,N,N,2] expected counts; hv_dec, hv_attach = (Hessian of
+ *   logZ) d: float32, each optional, fully written, zeros on the diagonal and outside the sentence.  All four of mu / hv NULL runs the
+ *   inside pass only.  An invalid length gives logZ = ev = NaN and zero mu / hv.  The table of vlg_deptree_expect holds with
+ *   arc -> (dec, attach).  ws holds vlg_dmv1o_expect_workspace(B, N, grad) bytes, grad = any of mu / hv wanted (0 where the charts fit
+ *   in LDS, and for arguments out of range).  VLG_ERR_SHAPE for N outside 2 ... 255, VLG_ERR_DTYPE, VLG_ERR_ARG for NULL dec / attach /
+ *   lengths / logZ, VLG_ERR_WORKSPACE; B = 0 is a no-op. */
+int vlg_dmv1o_expect(const void* dec, const void* attach, const void* v_dec, const void* v_attach, const void* v_sub_dec,
+                     const void* v_sub_attach, const int64_t* lengths, int B, int N, int in_dtype, int v_dtype, float* logZ, float* ev,
+                     float* mu_dec, float* mu_attach, float* hv_dec, float* hv_attach, void* ws, size_t ws_bytes, void* stream);
+size_t vlg_dmv1o_expect_workspace(int B, int N, int grad);
+
 /* The MBR decode of ldndmv.py:294-299 straight from the DMV1o arc marginals: DependencyCRF(marginals.sum(-1)).argmax.  marginals
  * [B,N,N,2] float32 (head, child, valence), as vlg_dmv1o_inside_outside / vlg_dmv1o_marginals_viterbi write grad_attach; the valence sum
  * is taken as the scores are loaded (no [B,N,N] intermediate).  heads / best_score as vlg_deptree_decode gives them on

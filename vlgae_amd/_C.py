@@ -71,6 +71,8 @@ SIGNATURES = {
     "vlg_deptree_kbest": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vlg_deptree_kbest_workspace": (_sz, [_i, _i, _i]),
     "vlg_deptree_expect": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "vlg_dmv1o_expect": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "vlg_dmv1o_expect_workspace": (_sz, [_i, _i, _i]),
     "vlg_eval_metrics_workspace": (_sz, [_i]),
     "vlg_eval_metrics": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "vlg_dmv1o_marginals_viterbi_supported": (_i, [_i]),

@@ -21,7 +21,7 @@ def _out_of_scope(name):
         f"StructDistribution.{name}: no caller in VLGAE uses it (only partition / max / argmax / marginals are "
         "reached; SURVEY.md section 2) -- outside the MI355X hot path this package implements.  (Drawing trees is "
         "implemented for DependencyCRF as `sample_heads` / `heads_to_parts` and for DMV1o as `sample_heads` / `log_prob_heads`; entropy, cross-entropy, KL and expected scores as "
-        "`tree_entropy` / `tree_cross_entropy` / `tree_kl` / `expected_score`; the k best trees as `kbest_heads` / `kbest_scores`.)")
+        "`tree_entropy` / `tree_cross_entropy` / `tree_kl` / `expected_score` on DependencyCRF and, for the DMV, on DMV1oExpect; the k best trees as `kbest_heads` / `kbest_scores`.)")
 
 
 class StructDistribution(Distribution):
@@ -181,6 +181,35 @@ class DMV1o(StructDistribution):
         """Root-augmented potentials (distributions.py:253-265): the root is token 0, generates only to
         the right, takes exactly the `root` scores with valence NOCHILD; everything else is `zero`."""
         return F.dmv1o_merge_autograd(dec, attach, root, one, zero)
+
+
+class DMV1oExpect(DMV1o):
+    """Extension (not in the reference): `DMV1o` with the expectation methods `DependencyCRF` has -- same constructor, same properties.
+    A class of its own: the surface of `DMV1o` is unchanged.  One dual-number inside-outside launch per distribution
+    (functional.dmv1o_expect), exact gradients.  The reference's names (`entropy`, `cross_entropy`, `kl`, `risk`,
+    distributions.py:79-114) stay out of scope under those names.  All return [B,1] like `partition` and are differentiable once with
+    respect to every potential; `other` may be any `DMV1o` over the same sentences."""
+
+    def expected_score(self, cost):
+        """E_p[<cost, tree>] for cost = (cost_dec [B,N,2,2,2], cost_attach [B,N,N,2]), either may be None: the reference's
+        `risk([cost_dec, cost_attach])`.  Gradient with respect to the cost: the expected counts."""
+        dec, attach = self.log_potentials
+        return F.dmv1o_expected_score(dec, attach, self.lengths, cost[0], cost[1])
+
+    def tree_entropy(self):
+        "H[p]: the reference's `entropy`."
+        dec, attach = self.log_potentials
+        return F.dmv1o_entropy(dec, attach, self.lengths)
+
+    def tree_cross_entropy(self, other):
+        "H[p, q] with q = `other` (a DMV1o over the same sentences): the reference's `cross_entropy(other)`."
+        dec, attach = self.log_potentials
+        return F.dmv1o_cross_entropy(dec, attach, other.log_potentials[0], other.log_potentials[1], self.lengths)
+
+    def tree_kl(self, other):
+        "KL[p || q] = H[p, q] - H[p]; exactly 0 with zero gradients when both hold the same potentials."
+        dec, attach = self.log_potentials
+        return F.dmv1o_kl(dec, attach, other.log_potentials[0], other.log_potentials[1], self.lengths)
 
 
 class DMV1oRules(StructDistribution):

@@ -717,6 +717,171 @@ def deptree_kl(arc_p, arc_q, lengths):
     return _DepTreeKL.apply(arc_p, arc_q, lengths)
 
 
+def dmv1o_expect(dec, attach, lengths, v=None, v_sub=None, want_mu=False, want_hv=False):
+    """Raw launcher of the dual-number DMV1o pass (vlg_dmv1o_expect).  dec [B,N,2,2,2], attach [B,N,N,2] root-merged; v, v_sub: pairs
+    (dec-shaped, attach-shaped) or None, either member may be None (= 0): the direction is v - v_sub.  Returns (logZ [B], ev [B] =
+    <mu, v - v_sub>, mu_dec, mu_attach, hv_dec, hv_attach), all float32; the mu pair is None unless want_mu, the hv pair = (Hessian of
+    logZ)(v - v_sub) None unless want_hv.  Without either only the inside pass runs.  One launch, no host synchronisation."""
+    _C.require_gpu(dec, "dmv1o_expect")
+    if dec.dim() != 5 or tuple(dec.shape[2:]) != (2, 2, 2):
+        raise ValueError(f"dec must be [B,N,2,2,2], got {tuple(dec.shape)}")
+    B, N = dec.shape[:2]
+    if tuple(attach.shape) != (B, N, N, 2):
+        raise ValueError(f"attach must be [B,N,N,2] = {(B, N, N, 2)}, got {tuple(attach.shape)}")
+    if dec.dtype != attach.dtype:
+        attach = attach.to(dec.dtype)
+    dt, dec_c = _C.in_dtype(dec)
+    _, att_c = _C.in_dtype(attach)
+    dirs = [*(v if v is not None else (None, None)), *(v_sub if v_sub is not None else (None, None))]   # v_dec, v_att, sub_dec, sub_att
+    given = [t for t in dirs if t is not None]
+    for k, t in enumerate(dirs):
+        if t is not None:
+            _C.require_gpu(t, "dmv1o_expect")
+            want = (B, N, 2, 2, 2) if k % 2 == 0 else (B, N, N, 2)
+            if tuple(t.shape) != want:
+                raise ValueError(f"direction must be (dec-shaped, attach-shaped) = ({(B, N, 2, 2, 2)}, {(B, N, N, 2)}), got {tuple(t.shape)}")
+    vdt = _C.F32
+    if given:   # the four directions in one storage type: bf16 only when every one given is bf16
+        if all(t.dtype == torch.bfloat16 for t in given):
+            vdt = _C.BF16
+        else:
+            dirs = [None if t is None else t.detach().float() for t in dirs]
+        dirs = [None if t is None else (t if t.is_contiguous() else t.contiguous()) for t in dirs]
+    lengths = _lengths(lengths, B, dec.device)
+    grad = want_mu or want_hv
+    dshape, ashape = (B, N, 2, 2, 2), (B, N, N, 2)
+    (logZ, ev, mu_d, mu_a, hv_d, hv_a), _ = _C.alloc_f32(dec.device, [(B,), (B,), dshape if want_mu else None, ashape if want_mu else None,
+                                                                      dshape if want_hv else None, ashape if want_hv else None])
+    L = _C.lib()
+    key = ("dmv1o_expect", B, N, grad)
+    nb = _WS_BYTES.get(key)
+    if nb is None:
+        nb = _WS_BYTES[key] = L.vlg_dmv1o_expect_workspace(B, N, int(grad))
+    ws = torch.empty(nb, dtype=torch.uint8, device=dec.device) if nb else None
+    _C.check(L.vlg_dmv1o_expect(_C.ptr(dec_c), _C.ptr(att_c), _C.ptr(dirs[0]), _C.ptr(dirs[1]), _C.ptr(dirs[2]), _C.ptr(dirs[3]), _C.ptr(lengths),
+                                B, N, dt, vdt, _C.ptr(logZ), _C.ptr(ev), _C.ptr(mu_d), _C.ptr(mu_a), _C.ptr(hv_d), _C.ptr(hv_a), _C.ptr(ws), nb,
+                                _C.stream_of(dec)), "dmv1o_expect")
+    return logZ, ev, mu_d, mu_a, hv_d, hv_a
+
+
+def _col(t, like):
+    "[B] float32 -> [B,1] in the dtype DMV1o.partition returns for these potentials"
+    return t.view(-1, 1).to(_out_dtype(like))
+
+
+class _DMV1oExpectedScore(torch.autograd.Function):
+    """E_p[<cost, tree>] (the reference's `risk`): value ev, d/d potentials = hv = Cov(tree, <cost, tree>), d/d cost = mu."""
+
+    @staticmethod
+    def forward(ctx, dec, attach, lengths, cost_dec, cost_attach):
+        need = ctx.needs_input_grad
+        _, ev, mu_d, mu_a, hv_d, hv_a = dmv1o_expect(dec, attach, lengths, v=(cost_dec, cost_attach), want_mu=need[3] or need[4],
+                                                     want_hv=need[0] or need[1])
+        ctx.save_for_backward(hv_d, hv_a, mu_d, mu_a)
+        ctx.in_dtypes = (dec.dtype, attach.dtype, None if cost_dec is None else cost_dec.dtype, None if cost_attach is None else cost_attach.dtype)
+        return _col(ev, dec)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        hv_d, hv_a, mu_d, mu_a = ctx.saved_tensors
+        need, dts = ctx.needs_input_grad, ctx.in_dtypes
+        gd, ga = _scale_counts(hv_d if need[0] else None, hv_a if need[1] else None, grad_out, dts[0], dts[1])
+        cd, ca = _scale_counts(mu_d if need[3] else None, mu_a if need[4] else None, grad_out, dts[2], dts[3])
+        return gd, ga, None, cd, ca
+
+
+class _DMV1oEntropy(torch.autograd.Function):
+    """H[p] = logZ - <mu, theta>: the direction is the distribution's own potentials; d/d theta = -hv."""
+
+    @staticmethod
+    def forward(ctx, dec, attach, lengths):
+        want = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        logZ, ev, _, _, hv_d, hv_a = dmv1o_expect(dec, attach, lengths, v=(dec, attach), want_hv=want)
+        ctx.save_for_backward(hv_d, hv_a)
+        ctx.in_dtypes = (dec.dtype, attach.dtype)
+        return _col(logZ - ev, dec)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        hv_d, hv_a = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gd, ga = _scale_counts(hv_d if need[0] else None, hv_a if need[1] else None, -grad_out, *ctx.in_dtypes)
+        return gd, ga, None
+
+
+def _dmv1o_pq(ctx, dec_p, att_p, dec_q, att_q, lengths, sub):
+    """The two launches cross-entropy and KL share (see _deptree_pq): p along v = theta_q (- theta_p when `sub`), q with no direction.
+    The q side runs the outside pass only when q wants a gradient (a fixed q costs one inside pass): the value pass of the inside-only
+    image and of the inside-outside image is the same sequence of operations (vlg_dmv_expect.h: dmv_expect_fw_span), so on equal
+    potentials the two logZ agree bit for bit whichever images ran."""
+    need = ctx.needs_input_grad
+    wp, wq = need[0] or need[1], need[2] or need[3]
+    logZ_p, ev, mu_d, mu_a, hv_d, hv_a = dmv1o_expect(dec_p, att_p, lengths, v=(dec_q, att_q), v_sub=(dec_p, att_p) if sub else None,
+                                                      want_mu=wq, want_hv=wp)
+    logZ_q, _, mq_d, mq_a, _, _ = dmv1o_expect(dec_q, att_q, lengths, want_mu=wq)
+    if wq:
+        mu_d.sub_(mq_d)          # in place: -(d/d theta_q) = mu_p - mu_q, scaled together with hv by -grad in backward
+        mu_a.sub_(mq_a)
+    ctx.save_for_backward(hv_d, hv_a, mu_d, mu_a)
+    ctx.in_dtypes = (dec_p.dtype, att_p.dtype, dec_q.dtype, att_q.dtype)
+    return logZ_p, logZ_q, ev
+
+
+def _dmv1o_pq_backward(ctx, grad_out):
+    hv_d, hv_a, dmu_d, dmu_a = ctx.saved_tensors
+    need, dts = ctx.needs_input_grad, ctx.in_dtypes
+    g = -grad_out
+    gpd, gpa = _scale_counts(hv_d if need[0] else None, hv_a if need[1] else None, g, dts[0], dts[1])
+    gqd, gqa = _scale_counts(dmu_d if need[2] else None, dmu_a if need[3] else None, g, dts[2], dts[3])
+    return gpd, gpa, gqd, gqa, None
+
+
+class _DMV1oCrossEntropy(torch.autograd.Function):
+    """H[p,q] = logZ_q - <mu_p, theta_q>; d/d theta_p = -hv, d/d theta_q = mu_q - mu_p."""
+
+    @staticmethod
+    def forward(ctx, dec_p, att_p, dec_q, att_q, lengths):
+        _, logZ_q, ev = _dmv1o_pq(ctx, dec_p, att_p, dec_q, att_q, lengths, False)
+        return _col(logZ_q - ev, dec_p)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        return _dmv1o_pq_backward(ctx, grad_out)
+
+
+class _DMV1oKL(torch.autograd.Function):
+    """KL[p||q] = logZ_q - logZ_p - <mu_p, theta_q - theta_p> (the subtraction is the kernel's v - v_sub); gradients as for H[p,q]."""
+
+    @staticmethod
+    def forward(ctx, dec_p, att_p, dec_q, att_q, lengths):
+        logZ_p, logZ_q, ev = _dmv1o_pq(ctx, dec_p, att_p, dec_q, att_q, lengths, True)
+        return _col(logZ_q - logZ_p - ev, dec_p)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        return _dmv1o_pq_backward(ctx, grad_out)
+
+
+def dmv1o_expected_score(dec, attach, lengths, cost_dec=None, cost_attach=None):
+    return _DMV1oExpectedScore.apply(dec, attach, lengths, cost_dec, cost_attach)
+
+
+def dmv1o_entropy(dec, attach, lengths):
+    return _DMV1oEntropy.apply(dec, attach, lengths)
+
+
+def dmv1o_cross_entropy(dec_p, att_p, dec_q, att_q, lengths):
+    return _DMV1oCrossEntropy.apply(dec_p, att_p, dec_q, att_q, lengths)
+
+
+def dmv1o_kl(dec_p, att_p, dec_q, att_q, lengths):
+    return _DMV1oKL.apply(dec_p, att_p, dec_q, att_q, lengths)
+
+
 def dmv1o_merge(dec, attach, root, one=0.0, zero=NEGINF):
     """DMV1o.merge (distributions.py:253-265): root-augmented potentials, always float32."""
     _C.require_gpu(dec, "dmv1o_merge")
