@@ -138,6 +138,13 @@ def main():
             print(f"{w:>3} {G:>3} {T:>2} {live:>4} {row['body_max']:>8.0f} {row['body_min']:>8.0f} {row['skew']:>6.0f} "
                   f"{row['bar']:>6.0f} {row['width']:>6.0f}")
         print(f"sum  width {tot['width']:.0f}  body_max {tot['body_max']:.0f}  skew {tot['skew']:.0f}  barrier {tot['bar']:.0f}")
+    # outside the passes (dmv_run's stamps, one row of 8 floats per wavefront in the last rows of grad_dec: slowest wavefront of a
+    # workgroup, median over the same workgroups): the load stage, the section between the passes, the count write-out
+    torch.cuda.synchronize()
+    rows = gdec.view(B, N, 8)[:KBLOCKS, N - 8:, :].flip(1).cpu().numpy()   # [block][wave][word]
+    stage, mid, out, passes = (float(np.median(rows[:, :, k].max(axis=1))) for k in (5, 6, 7, 4))
+    print("## outside the passes (cycles; slowest wavefront, median over the workgroups)")
+    print(f"load stage {stage:.0f}  between the passes {mid:.0f}  count write-out {out:.0f}  (inside start -> outside end {passes:.0f})")
 
 
 if __name__ == "__main__":

@@ -46,6 +46,7 @@
 #define VLG_HOSTDEV_M __host__ __device__
 #define VLG_EXP(x) __builtin_amdgcn_exp2f(x)   // v_exp_f32: 2^x
 #define VLG_LOG(x) __builtin_amdgcn_logf(x)    // v_log_f32: log2 x
+#define VLG_MULADD(a, b, c) __builtin_fmaf((a), (b), (c))   // a b + c in ONE rounding, where hipcc's contraction must not be left to chance
 #define VLG_BITS2F(u) __uint_as_float(u)
 #define VLG_ATOMIC_ADD(p, v) atomicAdd((p), (v))
 #else
@@ -59,6 +60,7 @@
 #define VLG_HOSTDEV_M
 #define VLG_EXP(x) exp2f(x)
 #define VLG_LOG(x) log2f(x)
+#define VLG_MULADD(a, b, c) ((a) * (b) + (c))   // (the host compiler contracts nothing, in either image)
 struct float2 { float x, y; };
 static inline float2 make_float2(float a, float b) { float2 r; r.x = a; r.y = b; return r; }
 static inline float vlg_bits2f(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
@@ -776,6 +778,24 @@ VLG_HD void dmv_bw_span(const DmvCtx& c, int w, int G, int D, bool live, int rr,
 // piece's last barrier.  tests/emu/plan_short.cpp replays the pass on counters and checks exactly this for every N, Ne, piece and lane.
 // (Storing the word only with its last contribution, r == w - 1, and at the piece's last width -- a nested, lane-dependent branch per
 // term -- made a two-term width body 167 instructions where this form has 138 and the parent 140: DESIGN.md section 7.)
+//
+// Stationary cells (round 12): each direction's SECOND stride-[0] walk.  On the left the column walk -- uu = CL(i + r, i).NC and its
+// gCc word through aUU -- on the right the row walk -- vv = IR(i, i + 1 + r) and its gI cell through aVV -- name the same cell at every
+// width of a piece.  dmv_bw_dir_p has the direction as a template parameter, so it knows which one: the value is read with the piece's
+// first value set only, and the adjoint word is held in BwHeld (guu | gvv) as gxa is: loaded at the piece's start, summed in the
+// register, written through.  Single owner, per word:
+//   gCc on or left of the diagonal, cell (i + r, i): stored only by the left column walk of the spans (i, i + w), w > r, at split
+//     point r.  The right direction's column walk falls on cells (k, j + 1), right of the diagonal; the own-cell access aGc is a read
+//     (ga, at width r: behind the barrier of the last contribution, which is in the chart).
+//   gI right of the diagonal, cell (i, i + 2 + r): stored by the right row walk of the spans (i, i + w), w > r + 1, at split point r
+//     (the left row walk falls on cells (j, i + r), left of the diagonal) -- and ONCE by the span (i, i + r + 1) itself, whose lane
+//     rr == 0 stores its complete adjoint gi there, its own cell.  At that width, w = r + 1, the holder's r is selfr: the guard
+//     r != selfr keeps it from adding or storing, its group reads the cell as gi_old through the chart, where the written-through sum
+//     is, and the store of gi follows inside the same wavefront's lockstep.  At every lower width the holder's term is dead (r >= w):
+//     its stale register is never used.
+// As for xa, the storing spans differ in w alone and (slot, rr, u) is one lane for the whole piece, also while it is not live yet; the
+// next piece's holder loads the word behind this piece's last barrier.  tests/emu/hold_short.cpp replays gCc and gI on counters and
+// checks exactly this, and every read through the chart, for every N, Ne, piece and lane.
 template <int TM>
 struct BwVals {
     float2 oc, sv, vv[TM];
@@ -895,8 +915,34 @@ VLG_HD FwAddr<DIR> dmv_fw_addr(const DmvCtx& c, int w, int D, int rr, X& x) {
 // That is both `r < w` and the right direction's `r <= w - 2`; the left direction's `r >= 1` holds for every term but the first
 // (u >= 1: r >= G >= 1).  So only the last term is compared with w (the right direction: with w - 1 as well), and only the left
 // direction's first term with 1.  Max semiring: am[] is rr + u G as before, so first-index-wins is untouched.
-template <int SR, bool BWD, int DIR, int G, int TU, typename X>
-VLG_HD void dmv_fw_span_p(const DmvCtx& c, const FwAddr<DIR>& a, int w, bool live, bool root_row, int rr, int D, X& x) {
+//
+// Stationary cells (round 12).  FwAddr::step() never moves eA, nor eU in the left direction, nor eV in the right one: over a piece a
+// lane's term u reads the same CR(i, i + r) and the same CL(i + r, i) | IR(i, i + 1 + r), r = rr + u G.  For u < TU - 1 that is
+// r <= (TU - 1) G - 1, so the cells have width <= (TU - 1) G -- written, and final, before the piece's first width -- and the piece
+// reads them ONCE, ahead of its width loop (FwHeld, NH = TU - 1 terms; dmv_fw_piece_p).  The last term's cells may be produced inside
+// the piece: it keeps its per-width loads.  NH = 0 is the body as it was: the TU = 1 pieces and the closed piece of the widths 1 and 2,
+// whose term count follows the width.  A dead or shadow lane holds whatever its address names, as it loaded it before, and never uses
+// it.  tests/emu/hold_short.cpp checks the producing widths and the addresses for every N, Ne, segment, piece, direction and lane.
+template <int DIR, int NH>
+struct FwHeld {
+    float av[NH > 0 ? NH : 1];    // CR(i, i + r)
+    float uu[NH > 0 ? NH : 1];    // DIR 0: CL(i + r, i).NC
+    float2 vv[NH > 0 ? NH : 1];   // DIR 1: IR(i, i + 1 + r)
+};
+
+template <int DIR, int G, int NH>
+VLG_HD void dmv_fw_load_held(const FwAddr<DIR>& a, FwHeld<DIR, NH>& h) {
+#pragma unroll
+    for (int u = 0; u < NH; ++u) {
+        h.av[u] = addr_ld<float>(a.eA, u * G * 8);
+        if constexpr (DIR == 0) h.uu[u] = addr_ld<float>(a.eU, u * a.gp8);
+        else h.vv[u] = addr_ld<float2>(a.eV, u * G * 8);
+    }
+}
+
+template <int SR, bool BWD, int DIR, int G, int TU, int NH, typename X>
+VLG_HD void dmv_fw_span_p(const DmvCtx& c, const FwAddr<DIR>& a, const FwHeld<DIR, NH>& h, int w, bool live, bool root_row, int rr, int D, X& x) {
+    static_assert(NH == 0 || NH == TU - 1, "every term but the last is held, or none");
     const float2 aX = addr_ld<float2>(a.oI);   // attach + dec[...,GO], staged at load
     const float cX = addr_ld<float>(a.cX);
     float m[3], s[3] = {0.f, 0.f, 0.f};
@@ -905,9 +951,10 @@ VLG_HD void dmv_fw_span_p(const DmvCtx& c, const FwAddr<DIR>& a, int w, bool liv
 #pragma unroll
     for (int u = 0; u < TU; ++u) {
         const int r = rr + u * G;
-        const float av = addr_ld<float>(a.eA, u * G * 8), bv = addr_ld<float>(a.eB, u * G * 8);
-        const float uu = addr_ld<float>(a.eU, u * a.gp8);
-        const float2 vv = addr_ld<float2>(a.eV, u * G * 8);
+        const bool held = u < NH;
+        const float av = held ? h.av[u] : addr_ld<float>(a.eA, u * G * 8), bv = addr_ld<float>(a.eB, u * G * 8);
+        const float uu = held && DIR == 0 ? h.uu[u] : addr_ld<float>(a.eU, u * a.gp8);
+        const float2 vv = held && DIR == 1 ? h.vv[u] : addr_ld<float2>(a.eV, u * G * 8);
         const bool last = u == TU - 1;
         const bool v0 = last ? r < w : true;
         const bool v1 = DIR == 0 ? (v0 && (u == 0 ? r >= 1 : true)) : (last ? r <= w - 2 : true);
@@ -964,11 +1011,15 @@ VLG_HD void dmv_fw_span_p(const DmvCtx& c, const FwAddr<DIR>& a, int w, bool liv
 template <int SR, bool BWD, int DIR, int LG, int TU, typename X>
 VLG_HD void dmv_fw_piece_p(const DmvCtx& c, FwAddr<DIR>& a, int wa, int wb, int slot, int wslot, int rr, int D, X& x) {
     constexpr int G = 1 << LG;
+    constexpr int NH = G > 1 ? TU - 1 : 0;   // terms whose stationary cells are read here, once (FwHeld); G = 1 is the closed piece w <= 2
+    if (NH > 0 && wa >= wb) return;          // (uniform over the workgroup) no width of this sentence has TU terms in this segment
+    FwHeld<DIR, NH> h;
+    dmv_fw_load_held<DIR, G, NH>(a, h);
     for (int w = wa; w < wb; ++w) {
         const int spans = x.uniform(c.Ne - w);
         const bool live = slot < spans;
         // (wave-uniform) a wavefront without a span of this width skips the body, not the step and the barrier
-        if (!(X::kSkipDeadWaves && wslot >= spans)) dmv_fw_span_p<SR, BWD, DIR, G, TU>(c, a, w, live, slot == 0, rr, D, x);
+        if (!(X::kSkipDeadWaves && wslot >= spans)) dmv_fw_span_p<SR, BWD, DIR, G, TU, NH>(c, a, h, w, live, slot == 0, rr, D, x);
         a.step();
         VLG_WSTAMP(x, 0, w, 0);
         x.sync();
@@ -1007,8 +1058,9 @@ VLG_HD void dmv_fw_segment_p(const DmvCtx& c, int w0, int w1, int tid, int nt, X
     else dmv_fw_dir_p<SR, BWD, 0, LG, TM>(c, w0, w1, t, x);
 }
 
-// the value reads of one width: the own cells and TM terms
-template <int G, int TM, bool XA = true>
+// the value reads of one width: the own cells and TM terms.  FIRST: the piece's first value set, with the stationary walks of direction
+// DIR -- xa, and uu (left) | vv (right); the refill leaves them out
+template <int DIR, int G, int TM, bool FIRST>
 VLG_HD void dmv_bw_load_vals(const BwAddr& a, BwVals<TM>& v) {
     v.oc = addr_ld<float2>(a.vC);
     v.Sv = addr_ld<float>(a.vS);
@@ -1016,10 +1068,29 @@ VLG_HD void dmv_bw_load_vals(const BwAddr& a, BwVals<TM>& v) {
     v.sv = addr_ld<float2>(a.vI);
 #pragma unroll
     for (int u = 0; u < TM; ++u) {
-        v.uu[u] = addr_ld<float>(a.vUU, u * a.gp8);
-        v.vv[u] = addr_ld<float2>(a.vVV, u * G * 8);
-        if constexpr (XA) v.xa[u] = addr_ld<float>(a.vXA, u * G * 8);   // stationary: read at the piece's start only
+        if constexpr (FIRST || DIR != 0) v.uu[u] = addr_ld<float>(a.vUU, u * a.gp8);
+        if constexpr (FIRST || DIR != 1) v.vv[u] = addr_ld<float2>(a.vVV, u * G * 8);
+        if constexpr (FIRST) v.xa[u] = addr_ld<float>(a.vXA, u * G * 8);
         v.xb[u] = addr_ld<float>(a.vXB, u * G * 8);
+    }
+}
+
+// The adjoint words a lane holds over a piece (the stationary walks of its direction): loaded at the piece's start, the width's weight
+// added where the parent added it to the word just read, the sum stored where the parent stored it.
+template <int DIR, int TM>
+struct BwHeld {
+    float gxa[TM];    // component of gCi[CR(i, i + r)]
+    float guu[TM];    // DIR 0: gCc[CL(i + r, i)]
+    float2 gvv[TM];   // DIR 1: gI[IR(i, i + 1 + r)]
+};
+
+template <int DIR, int G, int TM>
+VLG_HD void dmv_bw_load_held(const BwAddr& a, BwHeld<DIR, TM>& h) {
+#pragma unroll
+    for (int u = 0; u < TM; ++u) {
+        h.gxa[u] = addr_ld<float>(a.aXA, u * G * 8);
+        if constexpr (DIR == 0) h.guu[u] = addr_ld<float>(a.aUU, u * a.gp4);
+        else h.gvv[u] = addr_ld<float2>(a.aVV, u * G * 8);
     }
 }
 
@@ -1038,15 +1109,15 @@ struct BwAdj {
 
 // first half: the adjoint reads -- what the barrier was for -- and, while they are in flight, the weights' exponentials from registers
 // (adj_w = g * 2^min(t - out, 0): the factor first)
-template <int G, int TM, typename X>
+template <int DIR, int G, int TM, typename X>
 VLG_HD void dmv_bw_span_p1(const BwAddr& a, X& x, const BwVals<TM>& v, BwAdj<TM>& s) {
     s.ga = addr_ld<float>(a.aGc);
     s.gb = addr_ld<float2>(a.aGi);
     s.gi_old = addr_ld<float2>(a.aI);
 #pragma unroll
-    for (int u = 0; u < TM; ++u) {
-        s.o_gi[u] = addr_ld<float2>(a.aVV, u * G * 8);
-        s.o_c[u] = addr_ld<float>(a.aUU, u * a.gp4);
+    for (int u = 0; u < TM; ++u) {   // the moving walks; the stationary ones are in BwHeld
+        if constexpr (DIR == 0) s.o_gi[u] = addr_ld<float2>(a.aVV, u * G * 8);
+        else s.o_c[u] = addr_ld<float>(a.aUU, u * a.gp4);
         s.o_gb[u] = addr_ld<float>(a.aXB, u * G * 8);
     }
 #pragma unroll
@@ -1069,10 +1140,11 @@ VLG_HD void dmv_bw_span_p1(const BwAddr& a, X& x, const BwVals<TM>& v, BwAdj<TM>
     x.settle(s.s1);
 }
 
-// second half: the weights and the read-modify-writes.  gc_ok: the span is live and not the masked root cell; selfr: the split point
-// whose incomplete span has this same width.
-template <int G, int TM, typename X>
-VLG_HD void dmv_bw_span_p2(const BwAddr& a, int w, bool live, bool gc_ok, int rr, int selfr, X& x, const BwAdj<TM>& s, float (&gxa)[TM]) {
+// second half: the weights and the read-modify-writes.  gc_ok: the span is live and not the masked root cell; selfr (a constant 0 on
+// the left, w - 1 on the right): the split point whose incomplete span has this same width.
+template <int DIR, int G, int TM, typename X>
+VLG_HD void dmv_bw_span_p2(const BwAddr& a, int w, bool live, bool gc_ok, int rr, X& x, const BwAdj<TM>& s, BwHeld<DIR, TM>& h) {
+    const int selfr = DIR == 0 ? 0 : w - 1;
     float2 gc = make_float2(0.f, 0.f);                        // total adjoint of CL(j,i) | CR(i,j)
     if (gc_ok) gc = make_float2(s.gb.x, s.ga + s.gb.y);       // (zero for a dead lane and for the masked root cell, dmv.py:63)
     const float self0 = gc.x * s.s0, self1 = gc.y * s.s1;
@@ -1083,19 +1155,75 @@ VLG_HD void dmv_bw_span_p2(const BwAddr& a, int w, bool live, bool gc_ok, int rr
     for (int u = 0; u < TM; ++u) {
         const int r = rr + u * G;
         if (live && r < w) {
-            const float w0 = gc.x * s.e0[u], w1 = gc.y * s.e1[u], ws = gs * s.es[u];
-            if (r != selfr) addr_st(a.aVV, u * G * 8, make_float2(s.o_gi[u].x + w0, s.o_gi[u].y + w1));
-            addr_st(a.aUU, u * a.gp4, s.o_c[u] + (w0 + w1));
-            gxa[u] += ws;   // the stationary word of xa: summed in its register (the same addends in the same order), written through
-            addr_st(a.aXA, u * G * 8, gxa[u]);
-            addr_st(a.aXB, u * G * 8, s.o_gb[u] + ws);
+            // The roundings are those of the general image's code, which the tests compare with bit for bit -- there hipcc rounds the
+            // weights w0, w1 (each has a use that is no add) and contracts gs es into both of its adds.  With a held word as the addend
+            // it chose otherwise in places (round 12: w0 contracted into its adds where `r != selfr` is a constant, gxa and guu summed by
+            // one v_pk_add_f32 with gs es rounded first), so both are spelled out: w0, w1 settled, gs es + word as one operation.
+            float w0 = gc.x * s.e0[u], w1 = gc.y * s.e1[u];
+            x.settle(w0);
+            x.settle(w1);
+            // the stationary words: summed in their registers (the same addends in the same order), written through
+            if constexpr (DIR == 0) {
+                if (r != selfr) addr_st(a.aVV, u * G * 8, make_float2(s.o_gi[u].x + w0, s.o_gi[u].y + w1));
+                h.guu[u] += (w0 + w1);
+                addr_st(a.aUU, u * a.gp4, h.guu[u]);
+            } else {
+                // r == selfr (w = r + 1): the word is this span's own cell -- the group has read it as gi_old and lane rr == 0 stores gi
+                // into it below -- so the holder neither adds nor stores, and at every lower width its term is dead (r >= w)
+                if (r != selfr) {
+                    h.gvv[u] = make_float2(h.gvv[u].x + w0, h.gvv[u].y + w1);
+                    addr_st(a.aVV, u * G * 8, h.gvv[u]);
+                }
+                addr_st(a.aUU, u * a.gp4, s.o_c[u] + (w0 + w1));
+            }
+            h.gxa[u] = VLG_MULADD(gs, s.es[u], h.gxa[u]);
+            addr_st(a.aXA, u * G * 8, h.gxa[u]);
+            addr_st(a.aXB, u * G * 8, VLG_MULADD(gs, s.es[u], s.o_gb[u]));
         }
     }
     if (live && rr == 0) addr_st(a.aI, 0, gi);   // == d logZ / d attach[j,i,:] | attach[i,j,:]
 }
 
-// widths w1-1 ... w0 of one piece of the short-sentence image: groups of G lanes, one span per group and width (bw_capacity), every
-// width with w <= TM G -- the terms per lane that the single body runs (bw_terms)
+// widths w1-1 ... w0 of one piece of the short-sentence image, ONE direction: groups of G lanes, one span per group and width
+// (bw_capacity), every width with w <= TM G -- the terms per lane that the single body runs (bw_terms).  The direction is a template
+// parameter (round 12): dmv_bw_addr is called with a constant `right`, so the zero strides, the components of xa / xb, the split point
+// of the same-width term and the root row's mask are constants of the code, and which walks are stationary is known where the
+// registers that hold them are declared.
+template <int SR, int DIR, int G, int TM, typename X>
+VLG_HD void dmv_bw_dir_p(const DmvCtx& c, int w0, int w1, int t, X& x) {
+    const BwLane ln = bw_lane<G>(t);
+    const int rr = ln.rr, slot = ln.slot, wslot = ln.wslot;
+    const int D = slot < c.Ne - w0 ? VLG_MUL24(slot, c.P + 1) : 0;         // no span at any width of the piece (idle lanes too): shadow span 0
+    const int gc_hi = DIR == 1 && slot == 0 ? 1 : c.Ne;                    // CR(0, w): zero unless w == len, the width with ONE span (dmv.py:63)
+    BwAddr a = dmv_bw_addr<G>(c, w1 - 1, D, rr, DIR == 1, x);
+    // ONE register set of values and ONE place in the loop that refills it, for every wavefront: behind the last use of this width's
+    // values (the first half of the body), ahead of this width's stores (the second half).  No copies of the set.  At a segment's
+    // last width the refill reads the cells of width w0 - 1 >= 0 for nothing (the next segment, with its own group size, loads its
+    // own): a branch around it brings moves back, the set it skips and the set it loads meeting in a merge.
+    BwVals<TM> v;
+    dmv_bw_load_vals<DIR, G, TM, true>(a, v);
+    a.step_vals();
+    // the stationary cells of the piece (the table above BwAddr, stride [0]): xa and uu (left) | vv (right) stay in `v` -- the refill
+    // leaves them out -- and their adjoint words are held in `h` from here to the piece's end, written through with every contribution
+    BwHeld<DIR, TM> h;
+    dmv_bw_load_held<DIR, G, TM>(a, h);
+    for (int w = w1 - 1; w >= w0; --w) {
+        const int spans = x.uniform(c.Ne - w);   // (pinned to a scalar register, and the loop counter with it)
+        const bool live = slot < spans;
+        const bool body = !(X::kSkipDeadWaves && wslot >= spans);   // (wave-uniform) a wavefront without a span of this width: only the refill
+        BwAdj<TM> s;
+        if (body) dmv_bw_span_p1<DIR, G, TM>(a, x, v, s);
+        dmv_bw_load_vals<DIR, G, TM, false>(a, v);
+        if (body) dmv_bw_span_p2<DIR, G, TM>(a, w, live, live && spans <= gc_hi, rr, x, s, h);
+        a.step_vals();
+        a.step_adj();
+        VLG_WSTAMP(x, 1, w, 0);
+        x.sync();
+        VLG_WSTAMP(x, 1, w, 1);
+    }
+}
+
+// one piece, both directions: the (wave-uniform) direction is taken once per piece and never reaches a width loop, as in dmv_fw_segment_p
 template <int SR, int G, int TM, typename X>
 VLG_HD void dmv_bw_segment_p(const DmvCtx& c, int w0, int w1, int tid, int nt, X& x) {
     static_assert(G >= 1 && G <= 64 && TM >= 1 && G * TM <= 64, "a group sits in one wavefront; a lane's last term stays below split point 64");
@@ -1103,37 +1231,9 @@ VLG_HD void dmv_bw_segment_p(const DmvCtx& c, int w0, int w1, int tid, int nt, X
     if (w1 <= w0) return;
     const int nd = nt >> 1;
     const bool right = x.uniform(tid >= nd);
-    const BwLane ln = bw_lane<G>(dir_lane<VLG_MIRROR_RIGHT>(tid, nd, right));   // (dir_lane permutes whole wavefronts: groups are unchanged)
-    const int rr = ln.rr, slot = ln.slot, wslot = ln.wslot;
-    const int D = slot < c.Ne - w0 ? VLG_MUL24(slot, c.P + 1) : 0;         // no span at any width of the piece (idle lanes too): shadow span 0
-    const int gc_hi = right && slot == 0 ? 1 : c.Ne;                       // CR(0, w): zero unless w == len, the width with ONE span (dmv.py:63)
-    BwAddr a = dmv_bw_addr<G>(c, w1 - 1, D, rr, right, x);
-    // ONE register set of values and ONE place in the loop that refills it, for every wavefront: behind the last use of this width's
-    // values (the first half of the body), ahead of this width's stores (the second half).  No copies of the set.  At a segment's
-    // last width the refill reads the cells of width w0 - 1 >= 0 for nothing (the next segment, with its own group size, loads its
-    // own): a branch around it brings moves back, the set it skips and the set it loads meeting in a merge.
-    BwVals<TM> v;
-    dmv_bw_load_vals<G, TM>(a, v);
-    a.step_vals();
-    // the stationary cells of the piece (the table above BwAddr, stride [0] in both directions): xa stays in `v` -- the refill leaves it
-    // out -- and its adjoint word is held in gxa from here to the piece's end, written through with every contribution
-    float gxa[TM];
-#pragma unroll
-    for (int u = 0; u < TM; ++u) gxa[u] = addr_ld<float>(a.aXA, u * G * 8);
-    for (int w = w1 - 1; w >= w0; --w) {
-        const int spans = x.uniform(c.Ne - w), selfr = x.uniform(right ? w - 1 : 0);   // (pinned to scalar registers, and the loop counter with them)
-        const bool live = slot < spans;
-        const bool body = !(X::kSkipDeadWaves && wslot >= spans);   // (wave-uniform) a wavefront without a span of this width: only the refill
-        BwAdj<TM> s;
-        if (body) dmv_bw_span_p1<G, TM>(a, x, v, s);
-        dmv_bw_load_vals<G, TM, false>(a, v);
-        if (body) dmv_bw_span_p2<G, TM>(a, w, live, live && spans <= gc_hi, rr, selfr, x, s, gxa);
-        a.step_vals();
-        a.step_adj();
-        VLG_WSTAMP(x, 1, w, 0);
-        x.sync();
-        VLG_WSTAMP(x, 1, w, 1);
-    }
+    const int t = dir_lane<VLG_MIRROR_RIGHT>(tid, nd, right);   // (dir_lane permutes whole wavefronts: groups are unchanged)
+    if (right) dmv_bw_dir_p<SR, 1, G, TM>(c, w0, w1, t, x);
+    else dmv_bw_dir_p<SR, 0, G, TM>(c, w0, w1, t, x);
 }
 
 template <int SR, int DIR, int LG, int LONGSPAN, typename X>
@@ -1309,7 +1409,9 @@ VLG_HD void dmv_bw_segment(const DmvCtx& c, int w0, int w1, int tid, int nt, X& 
         // of the code, so each instruction-cache line serves eight wavefronts instead of four (the kernel is ~200 KB and 11 % of its wave
         // cycles wait for instructions); the direction-dependent indices become a few scalar selects per span.  Fused launch 75.8 ->
         // 75.5 us, bit-identical, half the outside-pass code.  (The same change in the inside pass costs 6 us: its direction-dependent
-        // predicates sit per term.)
+        // predicates sit per term.)  The short image no longer follows this since round 12: its pieces are ~150 instructions each, the
+        // whole kernel 38 KB with both directions' copies, and dmv_bw_dir_p takes the direction as a template parameter to know which
+        // walks stand still.
         dmv_bw_width<SR, -1, LG, LONGSPAN>(c, w, t, nd, x, right ? 1 : 0);
         x.sync();
     }
@@ -1764,6 +1866,9 @@ VLG_HD void dmv_walk(const DmvCtx& c, float g) {
 template <int SR, bool BWD, int LONGSPAN = false, typename IO, typename X>
 VLG_HD void dmv_run(const DmvCtx& c, const IO& io, float glogZ, float* logZ, int tid, int nt, X& x) {
     const int Ne = c.Ne, P = c.P, len = c.len;
+#if defined(VLG_STAMP) && defined(__HIPCC__)
+    const unsigned long long st_in = __builtin_amdgcn_s_memtime();   // diagnostic build: the load stage begins
+#endif
     // ---- stage: charts to the semiring zero (dmv.py:34-35), potentials into fast memory -------------------------
     // The potentials' global loads are issued first and land while the charts are being filled, so the launch pays
     // one memory latency, not one per dependent step.  Incomplete-span slots are pre-loaded with attach + dec[...,GO]
@@ -1808,12 +1913,13 @@ VLG_HD void dmv_run(const DmvCtx& c, const IO& io, float glogZ, float* logZ, int
     x.sync();
     // ---- inside -----------------------------------------------------------------------------------
 #if defined(VLG_STAMP) && defined(__HIPCC__)
-    unsigned long long st_body = 0, st_sync = 0, st_t0 = __builtin_amdgcn_s_memtime(), st_stage = 0, st_end = 0;
-    unsigned long long st_bbody = 0, st_bsync = 0;
+    unsigned long long st_body = 0, st_sync = 0, st_t0 = __builtin_amdgcn_s_memtime(), st_stage = st_t0 - st_in, st_end = 0;
+    unsigned long long st_bbody = 0, st_bsync = 0, st_mid0 = 0, st_mid = 0;   // st_stage: the load stage; st_mid: between the passes
     {   // (per-width body / barrier split is no longer taken: the width loop lives inside the segment functions)
         const unsigned long long a = __builtin_amdgcn_s_memtime();
         dmv_fw_all<SR, BWD, LONGSPAN>(c, tid, nt, x);
-        st_body += __builtin_amdgcn_s_memtime() - a;
+        st_mid0 = __builtin_amdgcn_s_memtime();
+        st_body += st_mid0 - a;
     }
 #else
     dmv_fw_all<SR, BWD, LONGSPAN>(c, tid, nt, x);
@@ -1856,6 +1962,7 @@ VLG_HD void dmv_run(const DmvCtx& c, const IO& io, float glogZ, float* logZ, int
 #if defined(VLG_STAMP) && defined(__HIPCC__)
     {
         const unsigned long long a = __builtin_amdgcn_s_memtime();
+        st_mid = a - st_mid0;   // logZ, the adjoint charts' zero fill, the root's cotangent and their barriers
         dmv_bw_all<SR, LONGSPAN>(cb, tid, nt, x);
         st_bbody += __builtin_amdgcn_s_memtime() - a;
     }
@@ -1913,11 +2020,12 @@ VLG_HD void dmv_run(const DmvCtx& c, const IO& io, float glogZ, float* logZ, int
         }
     }
 #if defined(VLG_STAMP) && defined(__HIPCC__)
+    const unsigned long long st_out = SR == VLG_SR_MAX ? 0 : __builtin_amdgcn_s_memtime() - st_end;   // the count write-out (Log: st_end is taken there)
     x.sync();
     if ((tid & 63) == 0) {   // diagnostic build only: per-wave cycle sums overwrite the (padded) last rows of grad_dec
         float* o = io.gdec + (size_t)(io.N - 1 - (tid >> 6)) * 8;
         o[0] = (float)st_body; o[1] = (float)st_sync; o[2] = (float)st_bbody; o[3] = (float)st_bsync;
-        o[4] = (float)(st_end - st_t0); o[5] = (float)st_stage; o[6] = 0.f; o[7] = 0.f;
+        o[4] = (float)(st_end - st_t0); o[5] = (float)st_stage; o[6] = (float)st_mid; o[7] = (float)st_out;
         float* o2 = io.gdec + (size_t)(io.N - 1 - 8 - (tid >> 6)) * 8;
         for (int k = 0; k < 8; ++k) o2[k] = (float)x.acc[k];
     }
