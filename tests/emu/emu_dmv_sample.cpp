@@ -1,31 +1,21 @@
 // emu_dmv_sample.cpp -- HOST EMULATOR of the DMV1o tree-sampling workgroup (vlgae_amd/csrc/vlg_dmv_sample.hip).  TEST INFRASTRUCTURE ONLY.
 //
 // The inside pass runs as in emu_dp.cpp (dmv_run<Log, false> through MergedIO under the token barrier, `nt` host threads as lanes);
-// behind it the SAME walk the gfx950 kernel runs (vlg_dmv_sample.h: dmv_sample_walk / dmv_sample_draw) draws every sample from the
-// charts, under a host policy whose "wavefront" is one lane: the wave operations become the sequential max / running sum / first match
-// they parallelise.  The charts and the walk's stack are carved as the kernel carves them -- the stack behind DmvLayout::lds_bytes, the
+// behind it the SAME walk the gfx950 kernel runs (vlg_dmv_sample.h: dmv_sample_walk, vlg_sample_common.h: sample_draw) draws every
+// sample from the charts, under the one-lane host policy of emu_sample_common.h.  The charts and the walk's stack are carved as the kernel carves them -- the stack behind DmvLayout::lds_bytes, the
 // charts in a second arena (the workspace) for the placements that move them there -- with the canary of emu_dp.cpp behind each arena.
 // Uniforms come from an explicit table only (the counter-based source is device code).
 //
 // Built two ways: as a shared library for ctypes calls (tests/test_dmv_sample_host.py), and, with -DEMU_DMV_SAMPLE_MAIN, as a
 // stand-alone program for the sanitizers, which replays a case file written by the test.
 #include "emu_dp.cpp"
+#include "emu_sample_common.h"
 
 #include "../../vlgae_amd/csrc/vlg_dmv_sample.h"
 
 #include <cstdio>
 
 namespace {
-
-struct DmvSeqX : HostX {
-    static constexpr int kWave = 1;
-    int lane() const { return 0; }
-    float wave_max(float v) { return v; }
-    float wave_scan(float v) { return v; }
-    float wave_last(float v) { return v; }
-    int ballot_first(bool p) { return p ? 0 : -1; }
-    int ballot_last(bool p) { return p ? 0 : -1; }
-};
 
 static int g_dmv_sample_mode = -1;   // the placement to emulate: -1 = the one dp_plan picks for this N (the launcher's), 0 / 1 forced
 
@@ -34,17 +24,9 @@ int dmv_sample_batch(const void* dec_, const void* attach_, const int64_t* lengt
                      float* logp, float* logZ, int nt, int order) {
     auto dec = (const typename In::T*)dec_;
     auto attach = (const typename In::T*)attach_;
-    const float nan = std::nanf("");
     for (int b = 0; b < B; ++b) {
         const int len = (int)lengths[b];
-        if (len < 1 || len > N - 1) {
-            if (logZ) logZ[b] = nan;
-            for (int s = 0; s < S; ++s) {
-                for (int i = 0; i < N; ++i) heads[((size_t)s * B + b) * N + i] = 0;
-                if (logp) logp[(size_t)s * B + b] = nan;
-            }
-            continue;
-        }
+        if (sample_no_sentence(len, b, B, N, S, heads, logp, logZ)) continue;
         const int mode = g_dmv_sample_mode >= 0 ? g_dmv_sample_mode : vlg::placement_of(vlg::dp_plan<vlg::DmvLayout>(N, false, false).image);
         const vlg::DmvLayout L(N, false, false, mode, false);
         Arena A(L.lds_bytes + vlg::kDmvSampleStack * sizeof(int)), W(L.ws_bytes);   // one wave's stack behind the charts' LDS
@@ -68,12 +50,9 @@ int dmv_sample_batch(const void* dec_, const void* attach_, const int64_t* lengt
         const float lz2 = c.C[len + 1].y;
         if (logZ) logZ[b] = lz2 * VLG_LN2;
         int* stack = (int*)A.at(L.lds_bytes);
-        DmvSeqX x{};
-        for (int s = 0; s < S; ++s) {
-            const vlg::DmvTableU us{u + ((size_t)s * B + b) * 3 * N * N, N};
-            vlg::dmv_sample_walk<In>(c, io.dec, io.attach, N, stack, us, heads + ((size_t)s * B + b) * N,
-                                     logp ? logp + (size_t)s * B + b : nullptr, lz2, x);
-        }
+        sample_each(b, B, N, S, u, heads, logp, [&](const vlg::TableU& us, long long* h, float* lp, SeqX& x) {
+            vlg::dmv_sample_walk<In>(c, io.dec, io.attach, N, stack, us, h, lp, lz2, x);
+        });
         A.check();
         W.check();
     }

@@ -1,14 +1,15 @@
 // emu_sample.cpp -- HOST EMULATOR of the tree-sampling workgroup (vlgae_amd/csrc/vlg_sample.hip).  TEST INFRASTRUCTURE ONLY.
 //
 // The inside pass runs as in emu_dp.cpp (dep_run under the token barrier, `nt` host threads as lanes); behind it the SAME walk the
-// gfx950 kernel runs (vlg_dp_sample.h: dep_sample_walk / dep_sample_draw) draws every sample from the charts, under a host policy
-// whose "wavefront" is one lane: the wave operations become the sequential max / running sum / first match they parallelise.
+// gfx950 kernel runs (vlg_dp_sample.h: dep_sample_walk, vlg_sample_common.h: sample_draw) draws every sample from the charts, under
+// the one-lane host policy of emu_sample_common.h.
 // The charts and the walk's stack are carved as the kernel carves them -- stack behind DepLayout::lds_bytes -- with the canary of
 // emu_dp.cpp behind each arena.  Uniforms come from an explicit table only (the counter-based source is device code).
 //
 // Built two ways: as part of a shared library for tests/emu/emu.py-style ctypes calls (tests/test_sample_host.py), and, with
 // -DEMU_SAMPLE_MAIN, as a stand-alone program for the sanitizers, which replays a case file written by the test.
 #include "emu_dp.cpp"
+#include "emu_sample_common.h"
 
 #include "../../vlgae_amd/csrc/vlg_dp_sample.h"
 
@@ -16,31 +17,13 @@
 
 namespace {
 
-struct SeqX : HostX {
-    static constexpr int kWave = 1;
-    int lane() const { return 0; }
-    float wave_max(float v) { return v; }
-    float wave_scan(float v) { return v; }
-    float wave_last(float v) { return v; }
-    int ballot_first(bool p) { return p ? 0 : -1; }
-    int ballot_last(bool p) { return p ? 0 : -1; }
-};
-
 template <typename In>
 int sample_batch(const void* arc_, const int64_t* lengths, int B, int N, int S, const float* u, long long* heads, float* logp,
                  float* logZ, int nt, int order) {
     auto arc = (const typename In::T*)arc_;
-    const float nan = std::nanf("");
     for (int b = 0; b < B; ++b) {
         const int len = lengths ? (int)lengths[b] : N - 1;
-        if (len < 1 || len > N - 1) {
-            if (logZ) logZ[b] = nan;
-            for (int s = 0; s < S; ++s) {
-                for (int i = 0; i < N; ++i) heads[((size_t)s * B + b) * N + i] = 0;
-                if (logp) logp[(size_t)s * B + b] = nan;
-            }
-            continue;
-        }
+        if (sample_no_sentence(len, b, B, N, S, heads, logp, logZ)) continue;
         const vlg::DepLayout L(N, false, false, g_dep_mode);
         Arena A(L.lds_bytes + vlg::kSampleStack * sizeof(int)), W(L.ws_bytes);   // one wave's stack behind the charts' LDS
         auto at = [&](const vlg::Region& r) { return r.lds ? A.at(r.off) : W.at(r.off); };
@@ -57,12 +40,9 @@ int sample_batch(const void* arc_, const int64_t* lengths, int B, int N, int S, 
         const float lz2 = c.C[len + 1];
         if (logZ) logZ[b] = lz2 * VLG_LN2;
         int* stack = (int*)A.at(L.lds_bytes);
-        SeqX x{};
-        for (int s = 0; s < S; ++s) {
-            const vlg::TableU us{u + ((size_t)s * B + b) * 3 * N * N, N};
-            vlg::dep_sample_walk<In>(c, arc_b, N, stack, us, heads + ((size_t)s * B + b) * N, logp ? logp + (size_t)s * B + b : nullptr,
-                                     lz2, x);
-        }
+        sample_each(b, B, N, S, u, heads, logp, [&](const vlg::TableU& us, long long* h, float* lp, SeqX& x) {
+            vlg::dep_sample_walk<In>(c, arc_b, N, stack, us, h, lp, lz2, x);
+        });
         A.check();
         W.check();
     }

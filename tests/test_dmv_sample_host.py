@@ -20,7 +20,8 @@ from conftest import GOLDEN, ROOT, golden_files, golden_ids, load
 HERE = os.path.join(ROOT, "tests", "emu")
 BUILD = os.path.join(HERE, "_build")
 SRC = os.path.join(HERE, "emu_dmv_sample.cpp")
-DEPS = [SRC, os.path.join(HERE, "emu_dp.cpp")] + [os.path.join(ROOT, "vlgae_amd", "csrc", f) for f in ("vlg_dp_core.h", "vlg_dmv_sample.h")]
+DEPS = [SRC, os.path.join(HERE, "emu_dp.cpp"), os.path.join(HERE, "emu_sample_common.h")] + [
+    os.path.join(ROOT, "vlgae_amd", "csrc", f) for f in ("vlg_dp_core.h", "vlg_dmv_sample.h", "vlg_sample_common.h")]
 FLOOR = 0.01
 SHAPE, DTYPE, WORKSPACE, NULL = 0x1001, 0x1002, 0x1004, 0x1005
 LDS_BUDGET = 160 * 1024

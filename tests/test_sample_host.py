@@ -23,7 +23,8 @@ from conftest import ROOT
 HERE = os.path.join(ROOT, "tests", "emu")
 BUILD = os.path.join(HERE, "_build")
 SRC = os.path.join(HERE, "emu_sample.cpp")
-DEPS = [SRC, os.path.join(HERE, "emu_dp.cpp")] + [os.path.join(ROOT, "vlgae_amd", "csrc", f) for f in ("vlg_dp_core.h", "vlg_dp_sample.h")]
+DEPS = [SRC, os.path.join(HERE, "emu_dp.cpp"), os.path.join(HERE, "emu_sample_common.h")] + [
+    os.path.join(ROOT, "vlgae_amd", "csrc", f) for f in ("vlg_dp_core.h", "vlg_dp_sample.h", "vlg_sample_common.h")]
 NS = (2, 3, 6, 41, 66)
 
 

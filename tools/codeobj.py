@@ -42,6 +42,7 @@ def kernels_of(obj_path):
             for k in meta.get("amdhsa.kernels", []):
                 rec = {key.lstrip("."): val for key, val in k.items() if key != ".args"}
                 rec["text_bytes"] = sizes.get(rec.get("name"), 0)
+                rec["kernarg"] = [(a.get(".size"), a.get(".offset"), a.get(".value_kind")) for a in k.get(".args", [])]
                 out.append(rec)
     if out:
         dem = subprocess.run(["c++filt"], input="\n".join(k["name"] for k in out), stdout=subprocess.PIPE, text=True).stdout.splitlines()
@@ -50,9 +51,9 @@ def kernels_of(obj_path):
     return out
 
 
-def all_kernels():
+def all_kernels(lib_dir=None):
     res = []
-    for obj in sorted(glob.glob(os.path.join(ROOT, "vlgae_amd", "_lib", "*.o"))):
+    for obj in sorted(glob.glob(os.path.join(lib_dir or os.path.join(ROOT, "vlgae_amd", "_lib"), "*.o"))):
         for k in kernels_of(obj):
             k["object"] = os.path.basename(obj)
             res.append(k)
@@ -74,7 +75,36 @@ def digests(lib_dir=None):
     return res
 
 
+def sections(lib_dir=None, names=(".text", ".rodata")):
+    """[(object name, section, sha256 of its bytes)] of every gfx950 code object: what two builds must share to run the same
+    instructions on the same constants, whatever else of the code object (symbol order, notes) moved."""
+    import hashlib
+    res = []
+    for obj in sorted(glob.glob(os.path.join(lib_dir or os.path.join(ROOT, "vlgae_amd", "_lib"), "*.o"))):
+        with tempfile.TemporaryDirectory() as td:
+            local = os.path.join(td, os.path.basename(obj))
+            shutil.copy(obj, local)
+            subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", local], cwd=td, stdout=subprocess.DEVNULL,
+                           stderr=subprocess.DEVNULL)
+            for co in sorted(glob.glob(os.path.join(td, "*gfx950*"))):
+                for sec in names:
+                    raw = os.path.join(td, "section.bin")
+                    subprocess.run([os.path.join(LLVM, "llvm-objcopy"), "-O", "binary", f"--only-section={sec}", co, raw], check=True)
+                    res.append((os.path.basename(obj), sec, hashlib.sha256(open(raw, "rb").read()).hexdigest()))
+    return res
+
+
 if __name__ == "__main__":
+    if "--sections" in sys.argv:   # one line per (object, section); diff the output of two builds
+        rest = [a for a in sys.argv[1:] if a != "--sections"]
+        for name, sec, sha in sections(rest[0] if rest else None):
+            print(name, sec, sha[:16])
+        sys.exit(0)
+    if "--notes" in sys.argv:      # one line per kernel with every figure of its note but the text size; diff the output of two builds
+        rest = [a for a in sys.argv[1:] if a != "--notes"]
+        for k in all_kernels(rest[0] if rest else None):
+            print(k["object"], {key: val for key, val in sorted(k.items()) if key not in ("object", "text_bytes")})
+        sys.exit(0)
     if "--digest" in sys.argv:
         rest = [a for a in sys.argv[1:] if a != "--digest"]
         for name, shas in digests(rest[0] if rest else None).items():

@@ -11,9 +11,8 @@
 //                IR(lo -> hi).v               r in [lo,hi)   t_r = CR(lo,r).HC + CL(hi,r+1).NC     (:54-56)
 //   draw kind 1  CL(hi -> lo).v               r in [lo,hi)   t_r = CL(r,lo).NC + IL(hi -> r).v     (:58-59)
 //   draw kind 2  CR(lo -> hi).v               r in (lo,hi]   t_r = IR(lo -> r).v + CR(r,hi).NC     (:61-62)
-// with the two cells of t_r as children.  The weights of a kind-0 cell do not depend on v but on the direction.  The draw itself --
-// w_r = 2^(t_r - max t), running sum, the strict cum_r > u total, the largest r of weight > 0 for u ~ 1 or NaN, never a split of
-// weight 0 -- is dep_sample_draw's rule (vlg_dp_sample.h), restated here over float2 charts: float pointers with a stride of two.
+// with the two cells of t_r as children.  The weights of a kind-0 cell do not depend on v but on the direction.  The draw itself is
+// vlg_sample_common.h's sample_draw, the one the DepTree sampler calls, over float2 charts: float pointers with a stride of two.
 // u is the cell's uniform, keyed (kind, lo, hi) as there: a derivation holds a span (kind, lo, hi) at most once, in one direction and
 // with one valence, so neither goes into the key.
 //
@@ -24,60 +23,11 @@
 // keeps both charts in LDS up to N = 99 and leaves 672 bytes there; eight stacks of 16 ints are 512.)
 #pragma once
 #include "vlg_dp_core.h"
+#include "vlg_sample_common.h"
 
 namespace vlg {
 
 constexpr int kDmvSampleStack = 16;   // ints per wavefront; the walk needs 7 (above) and checks
-
-// walk entries: 0 = IL(hi -> lo), 1 = CL(hi -> lo), 2 = CR(lo -> hi), 3 = IR(lo -> hi), each with a valence; the draw kind of both
-// incomplete cells is 0
-VLG_HD int dmv_sample_entry(int kind, int lo, int hi, int v) { return kind | (lo << 2) | (hi << 10) | (v << 18); }
-
-// the uniforms of one (sample, sentence) from the explicit table u [S,B,3,N,N]
-struct DmvTableU {
-    const float* u;   // at [s][b]
-    int N;
-    VLG_HDM float get(int kind, int lo, int hi) const { return u[((size_t)kind * N + lo) * N + hi]; }
-};
-
-// One draw: the index k of the split taken among the n terms t_k = a[k sa] + b[k sb] under u.  Every lane of the wave returns the
-// same k.  X::kWave lanes spread over the terms, 'kWave' at a time.
-template <typename X>
-VLG_HD int dmv_sample_draw(const float* a, int sa, const float* b, int sb, int n, float u, X& x) {
-    constexpr int W = X::kWave;
-    const int lane = x.lane();
-    if (n <= W) {   // one chunk (always, for N <= 65 on the device): the terms stay in registers -- the same operations as the loops below
-        const bool in = lane < n;
-        const float t = in ? a[lane * sa] + b[lane * sb] : VLG_LOWEST;
-        const float m1 = x.wave_max(t), w1 = in ? VLG_EXP(t - m1) : 0.f, cum = x.wave_scan(w1);
-        int pick = x.ballot_first(cum > u * x.wave_last(cum) && w1 > 0.f);
-        if (pick < 0) pick = x.ballot_last(w1 > 0.f);
-        return pick < 0 ? 0 : pick;
-    }
-    float m = VLG_LOWEST;
-    for (int k = lane; k < n; k += W) m = fmaxf(m, a[k * sa] + b[k * sb]);
-    m = x.wave_max(m);
-    // the weights of the chunk at k0 and their running sum behind `carry`; w = 0 past the last term
-    auto chunk = [&](int k0, float carry, float& w) {
-        const int k = k0 + lane;
-        w = k < n ? VLG_EXP(a[k * sa] + b[k * sb] - m) : 0.f;
-        return carry + x.wave_scan(w);
-    };
-    float total = 0.f, w;
-    for (int k0 = 0; k0 < n; k0 += W) total = x.wave_last(chunk(k0, total, w));
-    const float thr = u * total;
-    float carry = 0.f;
-    int pick = -1, last = -1;   // carried over the chunks: the split taken, the largest k of weight > 0 so far
-    for (int k0 = 0; k0 < n && pick < 0; k0 += W) {
-        const float cum = chunk(k0, carry, w);
-        const int f = x.ballot_first(cum > thr && w > 0.f), l = x.ballot_last(w > 0.f);
-        if (f >= 0) pick = k0 + f;
-        if (l >= 0) last = k0 + l;
-        carry = x.wave_last(cum);
-    }
-    if (pick < 0) pick = last;
-    return pick < 0 ? 0 : pick;   // (no term of weight > 0: only a damaged chart; the walk's visit bound ends it)
-}
 
 // The terms of walk cell (kind, lo, hi, v) as two strided float walks over the float2 charts (component = valence).
 VLG_HD void dmv_sample_terms(const DmvCtx& c, int kind, int lo, int hi, int v, const float*& a, int& sa, const float*& b, int& sb) {
@@ -120,9 +70,9 @@ VLG_HD void dmv_sample_walk(const DmvCtx& c, const typename In::T* dec, const ty
     using T = typename In::T;
     T raw_att = T(), raw_go = T(), raw_stop_a = T(), raw_stop_b = T();
     bool has_arc = false, has_stop_a = false, has_stop_b = false;
-    int e = dmv_sample_entry(2, 0, len, 1);
+    int e = sample_entry(2, 0, len, 1);
     for (;;) {
-        const int kind = e & 3, lo = (e >> 2) & 255, hi = (e >> 10) & 255, v = (e >> 18) & 1;
+        const int kind = entry_kind(e), lo = entry_lo(e), hi = entry_hi(e), v = entry_v(e);
         if (++visits > 4 * N) { ok = false; break; }
         const int dk = kind == 3 ? 0 : kind;
         if (dk == 0) {
@@ -139,46 +89,32 @@ VLG_HD void dmv_sample_walk(const DmvCtx& c, const typename In::T* dec, const ty
             const float *a, *b;
             int sa, sb;
             dmv_sample_terms(c, kind, lo, hi, v, a, sa, b, sb);
-            k = x.uniform(dmv_sample_draw(a, sa, b, sb, hi - lo, us.get(dk, lo, hi), x));
+            k = x.uniform(sample_draw(a, sa, b, sb, hi - lo, us.get(dk, lo, hi), x));
         }
-        int ea, eb;   // the two children
-        if (kind == 0) { ea = dmv_sample_entry(2, lo, lo + k, 1); eb = dmv_sample_entry(1, lo + k + 1, hi, 0); }
-        else if (kind == 3) { ea = dmv_sample_entry(2, lo, lo + k, 0); eb = dmv_sample_entry(1, lo + k + 1, hi, 1); }
-        else if (kind == 1) { ea = dmv_sample_entry(1, lo, lo + k, 1); eb = dmv_sample_entry(0, lo + k, hi, v); }
-        else { ea = dmv_sample_entry(3, lo, lo + 1 + k, v); eb = dmv_sample_entry(2, lo + 1 + k, hi, 1); }
-        int wa = ((ea >> 10) & 255) - ((ea >> 2) & 255), wb = ((eb >> 10) & 255) - ((eb >> 2) & 255);
-        if (wa > wb) { const int t = ea; ea = eb; eb = t; const int tw = wa; wa = wb; wb = tw; }   // ea: the narrower one
+        int ea, eb, wa, wb;   // the two children
+        if (kind == 0) { ea = sample_entry(2, lo, lo + k, 1); eb = sample_entry(1, lo + k + 1, hi, 0); }
+        else if (kind == 3) { ea = sample_entry(2, lo, lo + k, 0); eb = sample_entry(1, lo + k + 1, hi, 1); }
+        else if (kind == 1) { ea = sample_entry(1, lo, lo + k, 1); eb = sample_entry(0, lo + k, hi, v); }
+        else { ea = sample_entry(3, lo, lo + 1 + k, v); eb = sample_entry(2, lo + 1 + k, hi, 1); }
+        sample_order(ea, eb, wa, wb);
         if (has_stop_a) score += In::ld(&raw_stop_a, 0);
         if (has_stop_b) score += In::ld(&raw_stop_b, 0);
         has_stop_a = wa == 0;
         has_stop_b = wb == 0;
         if (has_stop_a) {   // a width-0 complete cell C(h,h).v (an incomplete cell is >= 1 wide): the STOP of h towards CL's / CR's side
-            const int h = (ea >> 2) & 255, dir = (ea & 3) == 1 ? 0 : 1;
-            raw_stop_a = dec[(size_t)h * 8 + dec_idx(dir, (ea >> 18) & 1, 1)];
+            const int h = entry_lo(ea), dir = entry_kind(ea) == 1 ? 0 : 1;
+            raw_stop_a = dec[(size_t)h * 8 + dec_idx(dir, entry_v(ea), 1)];
         }
         if (has_stop_b) {
-            const int h = (eb >> 2) & 255, dir = (eb & 3) == 1 ? 0 : 1;
-            raw_stop_b = dec[(size_t)h * 8 + dec_idx(dir, (eb >> 18) & 1, 1)];
+            const int h = entry_lo(eb), dir = entry_kind(eb) == 1 ? 0 : 1;
+            raw_stop_b = dec[(size_t)h * 8 + dec_idx(dir, entry_v(eb), 1)];
         }
-        if (wa > 0) {
-            if (top >= kDmvSampleStack) { ok = false; break; }
-            stack[top++] = eb;   // (wb >= wa > 0)
-            e = ea;
-        } else if (wb > 0) {
-            e = eb;
-        } else {
-            if (top == 0) break;
-            e = x.uniform(stack[--top]);
-        }
+        if (!sample_step(stack, kDmvSampleStack, top, ea, eb, wa, wb, e, ok, x)) break;
     }
     if (has_arc) score += In::ld(&raw_att, 0) + In::ld(&raw_go, 0);
     if (has_stop_a) score += In::ld(&raw_stop_a, 0);
     if (has_stop_b) score += In::ld(&raw_stop_b, 0);
-    if (lane == 0) {
-        if (!ok)
-            for (int i = 0; i < N; ++i) heads[i] = 0;   // one lane, in program order behind its own stores above
-        if (logp) *logp = ok ? score - lz2 * VLG_LN2 : VLG_BITS2F(0x7fc00000u);
-    }
+    sample_finish(ok, score, lz2, N, heads, logp, lane);
 }
 
 }  // namespace vlg

@@ -6,64 +6,14 @@
 // vlg_deptree_inside does (dep_run, same chart placement: LDS where the charts fit, the VLG_OP_DEPTREE_INSIDE workspace otherwise).
 // Behind the last barrier of that pass the charts are read-only and the eight wavefronts part ways: each owns whole samples
 // (s = first + wave, + 8, ...), lanes spread over the split points of the cell being drawn.  No barrier, no atomics, one writer per
-// output element.  The per-wave stacks sit in dynamic LDS behind DepLayout::lds_bytes.
-#include "vlg_dp_kernels.h"
+// output element.  The per-wave stacks sit in dynamic LDS behind DepLayout::lds_bytes.  The frame -- wave policy, uniforms, grid,
+// checks, image dispatch -- is vlg_sample_kernels.h's, shared with the DMV1o sampler.
+#include "vlg_sample_kernels.h"
 #include "vlg_dp_sample.h"
-#include "vlg_rng.h"
 
 namespace vlg {
 
-constexpr int kSampleWaves = kThreads / 64;
 constexpr size_t kSampleStackBytes = (size_t)kSampleWaves * kSampleStack * sizeof(int);
-// Workgroups that fill the device once: kSampleCUs x the workgroups of this N that share a CU -- as many as its LDS holds, at most
-// kSampleBlocksPerCU (a workgroup is eight of a CU's wavefront slots).  The walk is a chain of dependent LDS reads and cross-lane steps: further
-// workgroups on the CU hide its latencies (B = 256, N = 41, S = 64: 462 us with one per CU, 366 us with two).
-constexpr int kSampleCUs = 256, kSampleBlocksPerCU = 4;
-
-// the wave operations of the walk on a wavefront whose 64 lanes are all active (the walk's control flow is wave-uniform)
-struct SampleX : DevX {
-    static constexpr int kWave = 64;
-    __device__ __forceinline__ int lane() const { return (int)(threadIdx.x & 63); }
-    __device__ __forceinline__ float wave_max(float v) {
-        allreduce_max<1>(&v, 64);
-        return v;
-    }
-    // Inclusive prefix sum over the 64 lanes without LDS traffic: a shift-and-add scan inside each row of 16 lanes (DPP row_shr 1, 2, 4, 8; a lane
-    // without a source adds 0), then the row totals carried on: row_bcast:15 hands lane 15 of rows 0 and 2 to rows 1 and 3, row_bcast:31 lane 31
-    // to rows 2 and 3.  (The partial sums are rounded in another order than a sequential sum: see dep_sample_draw's w > 0.)
-    __device__ __forceinline__ float wave_scan(float v) {
-#define VLG_SCAN_STEP(CTRL, ROWS) v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROWS, 0xf, false))
-        VLG_SCAN_STEP(0x111, 0xf);   // row_shr:1
-        VLG_SCAN_STEP(0x112, 0xf);   // row_shr:2
-        VLG_SCAN_STEP(0x114, 0xf);   // row_shr:4
-        VLG_SCAN_STEP(0x118, 0xf);   // row_shr:8
-        VLG_SCAN_STEP(0x142, 0xa);   // row_bcast:15 -> rows 1, 3
-        VLG_SCAN_STEP(0x143, 0xc);   // row_bcast:31 -> rows 2, 3
-#undef VLG_SCAN_STEP
-        return v;
-    }
-    __device__ __forceinline__ float wave_last(float v) {   // the last lane's value: the total of an inclusive scan
-        return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-    }
-    __device__ __forceinline__ int ballot_first(bool p) {   // lowest lane where p holds, -1 if none
-        const unsigned long long m = __ballot(p);
-        return m ? (int)__ffsll((long long)m) - 1 : -1;
-    }
-    __device__ __forceinline__ int ballot_last(bool p) {    // highest such lane
-        const unsigned long long m = __ballot(p);
-        return m ? 63 - (int)__clzll((long long)m) : -1;
-    }
-};
-
-// the uniforms of one (sample, sentence) from the counter-based generator (vlg_rng.h)
-struct PhiloxU {
-    uint2 key;
-    uint32_t s, b, step;
-    __device__ __forceinline__ float get(int kind, int lo, int hi) const {
-        const uint4 r = philox4x32_10(make_uint4((uint32_t)(kind << 16 | hi << 8 | lo), s, b, step), key);
-        return (float)(r.x >> 8) * (1.0f / 16777216.0f);   // 24 bits: exact in fp32, < 1
-    }
-};
 
 template <int MODE, typename In>
 __global__ __launch_bounds__(kThreads) void deptree_sample_kernel(const typename In::T* __restrict__ arc, const int64_t* __restrict__ lengths,
@@ -75,15 +25,7 @@ __global__ __launch_bounds__(kThreads) void deptree_sample_kernel(const typename
     const int b = blockIdx.x, B = gridDim.x, tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: the keys, the counters and the stack address stay scalar
     const int s0 = blockIdx.y * per_block, s1 = s0 + per_block < S ? s0 + per_block : S;   // this block's samples
     const int len = lengths ? (int)lengths[b] : N - 1;
-    const float nan = __uint_as_float(0x7fc00000u);
-    if (len < 1 || len > N - 1) {   // not a sentence (block-uniform): the convention of vlg_deptree_decode
-        if (blockIdx.y == 0 && tid == 0 && logZ) logZ[b] = nan;
-        for (int s = s0; s < s1; ++s) {
-            for (int i = tid; i < N; i += kThreads) heads[((size_t)s * B + b) * N + i] = 0;
-            if (tid == 0 && logp) logp[(size_t)s * B + b] = nan;
-        }
-        return;
-    }
+    if (len < 1 || len > N - 1) return sample_no_sentence(N, s0, s1, heads, logp, logZ);
     char* wsb = ws + ((size_t)blockIdx.y * B + b) * ws_stride;
     const DepCtx c = carve_dep<VLG_SR_LOG, MODE, false>(N, len, smem, wsb);
     const typename In::T* arc_b = arc + (size_t)b * N * N;
@@ -108,71 +50,27 @@ __global__ __launch_bounds__(kThreads) void deptree_sample_kernel(const typename
     }
 }
 
-struct SampleArgs {
-    const void* arc;
-    const int64_t* lengths;
-    int B, N, S, Y;
-    const uint64_t* rng;
-    unsigned site;
-    const float* u;
-    int64_t* heads;
-    float *logp, *logZ;
-    void* ws;
-    size_t ws_stride, lds_charts;
-    hipStream_t s;
-};
-
-template <int MODE, typename In>
-static int launch_sample(const SampleArgs& a) {
-    const size_t lds = a.lds_charts + kSampleStackBytes;
-    return launch("deptree_sample_kernel", deptree_sample_kernel<MODE, In>, dim3(a.B, a.Y), dim3(kThreads), lds, a.s, (const typename In::T*)a.arc, a.lengths,
-                  a.N, a.S, (a.S + a.Y - 1) / a.Y, a.rng, a.site, a.u, (long long*)a.heads, a.logp, a.logZ, (char*)a.ws, a.ws_stride, a.lds_charts);
-}
-
-template <typename In>
-static int launch_sample_mode(int mode, const SampleArgs& a) {
-    if (mode == kModeShort) return launch_sample<kModeShort, In>(a);
-    return mode == 0 ? launch_sample<0, In>(a) : launch_sample<1, In>(a);
-}
-
-// Blocks per sentence: enough that B Y workgroups fill the device once, never more than the samples can feed (a wavefront owns whole
-// samples: ceil(S / 8) blocks have one each).  Every further block repeats the inside pass, so Y = 1 as soon as B alone fills the device.
-static int sample_blocks(const DpPlan& p, int B, int S) {
-    size_t per_cu = kLdsBudget / (p.lds_bytes + kSampleStackBytes);
-    per_cu = per_cu < 1 ? 1 : per_cu > (size_t)kSampleBlocksPerCU ? (size_t)kSampleBlocksPerCU : per_cu;
-    if (p.ws_stride) per_cu = 1;   // charts in the workspace: every block needs its own slice of it (0.5 MB at N = 255), and its inside pass is the slow one
-    const int fill = kSampleCUs * (int)per_cu;
-    const int want = B >= fill ? 1 : fill / B, cap = (S + kSampleWaves - 1) / kSampleWaves;
-    return want < cap ? want : cap;
-}
-
 }  // namespace vlg
 
 extern "C" {
 
 int vlg_deptree_sample_blocks(int B, int N, int S) {
     if (B < 1 || S < 1 || N < 2 || N > 255) return 1;
-    return vlg::sample_blocks(vlg::dp_plan<vlg::DepLayout>(N, false, false), B, S);
+    return vlg::sample_blocks(vlg::dp_plan<vlg::DepLayout>(N, false, false), vlg::kSampleStackBytes, B, S);
 }
 
+// ws: one slice per block of the (B, Y) grid, vlg_workspace_bytes(VLG_OP_DEPTREE_INSIDE, B * vlg_deptree_sample_blocks(B, N, S), N, 0)
 int vlg_deptree_sample(const void* arc, const int64_t* lengths, int B, int N, int in_dtype, int S, const uint64_t* rng, unsigned site,
                        const float* u, int64_t* heads, float* logp, float* logZ, void* ws, size_t ws_bytes, void* stream) {
     using namespace vlg;
-    if (int e = check_dp_args("deptree_sample", B, N, VLG_F32, VLG_SR_LOG)) return e;   // the shape; the dtype's turn is behind S
-    if (S < 1) return set_error(VLG_ERR_SHAPE, "deptree_sample: need S >= 1 samples (got %d)", S);
-    if (in_dtype != VLG_F32 && in_dtype != VLG_BF16) return set_error(VLG_ERR_DTYPE, "deptree_sample: in_dtype %d", in_dtype);
-    if (B == 0) return 0;
-    if ((rng != nullptr) == (u != nullptr))
-        return set_error(VLG_ERR_NULL, "deptree_sample: pass exactly one of rng (counter-based draws) and u (explicit uniforms)");
-    if (!arc || !heads) return set_error(VLG_ERR_NULL, "deptree_sample: null buffer");
-    const DpPlan p = dp_plan<DepLayout>(N, false, false);   // the plan of vlg_deptree_inside
-    const int Y = sample_blocks(p, B, S);
-    if (p.lds_bytes + kSampleStackBytes > kLdsBudget)
-        return set_error(VLG_ERR_SHAPE, "deptree_sample: N=%d leaves no LDS for the walk's stacks", N);   // (not reached for N <= 255)
-    // one slice per block of the (B, Y) grid: vlg_workspace_bytes(VLG_OP_DEPTREE_INSIDE, B * vlg_deptree_sample_blocks(B, N, S), N, 0)
-    if (int e = check_dp_workspace("deptree_sample", N, p, (size_t)B * Y, ws, ws_bytes)) return e;
-    const SampleArgs a{arc, lengths, B, N, S, Y, rng, site, u, heads, logp, logZ, ws, p.ws_stride, p.lds_bytes, (hipStream_t)stream};
-    return in_dtype == VLG_F32 ? launch_sample_mode<F32In>(p.image, a) : launch_sample_mode<BF16In>(p.image, a);
+    SampleArgs a{lengths, B, N, S, rng, site, u, heads, logp, logZ, ws, (hipStream_t)stream};
+    const int e = sample_check<DepLayout>("deptree_sample", kSampleStackBytes, in_dtype, arc && heads, ws_bytes, a);   // the plan of vlg_deptree_inside
+    if (e || !a.Y) return e;
+    return sample_dispatch(in_dtype, a.image, [&](auto mode, auto in) {
+        using In = decltype(in);
+        return launch_sample("deptree_sample_kernel", deptree_sample_kernel<decltype(mode)::value, In>, kSampleStackBytes, a,
+                             (const typename In::T*)arc);
+    });
 }
 
 }  // extern "C"

@@ -226,6 +226,23 @@ def deptree_decode(arc, lengths=None):
     return best, heads
 
 
+def _sample_frame(name, device, B, N, n, rng, site, u, want_logp):
+    """What deptree_sample and dmv1o_sample share: exactly one of rng and u, the shape of u, the outputs heads [n,B,N] / logp [n,B]
+    or None / logZ [B], and the C arguments `rng, site, u, heads, logp, logZ` of vlg_*_sample.  Returns (heads, logp, logZ, u, args);
+    u is the contiguous table the arguments point into."""
+    if (rng is None) == (u is None):
+        raise ValueError(f"{name}: pass exactly one of rng and u")
+    if u is not None:
+        if tuple(u.shape) != (n, B, 3, N, N) or u.dtype != torch.float32 or u.device != device:
+            raise ValueError(f"{name}: u must be float32 [n,B,3,N,N] = {(n, B, 3, N, N)} on {device}")
+        u = u.contiguous()
+    heads = torch.empty((n, B, N), dtype=torch.int64, device=device)
+    logp = torch.empty((n, B), dtype=torch.float32, device=device) if want_logp else None
+    logZ = torch.empty(B, dtype=torch.float32, device=device)
+    args = (None if rng is None else _C.ptr(rng.state), int(site), _C.ptr(u), _C.ptr(heads), _C.ptr(logp), _C.ptr(logZ))
+    return heads, logp, logZ, u, args
+
+
 def deptree_sample(arc, lengths, n, rng=None, site=0, u=None, want_logp=True):
     """n trees per sentence drawn from the projective CRF of arc scores [B,N,N], in ONE launch (vlg_deptree_sample):
     (heads [n,B,N] int64 as deptree_decode writes them, logp [n,B] float32 or None, logZ [B]).  The uniforms come either from
@@ -239,21 +256,11 @@ def deptree_sample(arc, lengths, n, rng=None, site=0, u=None, want_logp=True):
     n = int(n)
     dt, arc_c = _C.in_dtype(arc)
     lengths = _lengths(lengths, B, arc.device, allow_none=True)
-    if (rng is None) == (u is None):
-        raise ValueError("deptree_sample: pass exactly one of rng and u")
-    if u is not None:
-        if tuple(u.shape) != (n, B, 3, N, N) or u.dtype != torch.float32 or u.device != arc.device:
-            raise ValueError(f"deptree_sample: u must be float32 [n,B,3,N,N] = {(n, B, 3, N, N)} on {arc.device}")
-        u = u.contiguous()
-    heads = torch.empty((n, B, N), dtype=torch.int64, device=arc.device)
-    logp = torch.empty((n, B), dtype=torch.float32, device=arc.device) if want_logp else None
-    logZ = torch.empty(B, dtype=torch.float32, device=arc.device)
+    heads, logp, logZ, u, args = _sample_frame("deptree_sample", arc.device, B, N, n, rng, site, u, want_logp)
     L = _C.lib()
     blocks = L.vlg_deptree_sample_blocks(B, N, n) if B > 0 and n > 0 else 1
     ws, nb = _workspace(_C.OP_DEPTREE_INSIDE, B * blocks, N, _C.SEMIRING_LOG, arc.device)
-    _C.check(L.vlg_deptree_sample(_C.ptr(arc_c), _C.ptr(lengths), B, N, dt, n, None if rng is None else _C.ptr(rng.state), int(site),
-                                  _C.ptr(u), _C.ptr(heads), _C.ptr(logp), _C.ptr(logZ), _C.ptr(ws), nb, _C.stream_of(arc)),
-             "deptree_sample")
+    _C.check(L.vlg_deptree_sample(_C.ptr(arc_c), _C.ptr(lengths), B, N, dt, n, *args, _C.ptr(ws), nb, _C.stream_of(arc)), "deptree_sample")
     return heads, logp, logZ
 
 
@@ -274,20 +281,11 @@ def dmv1o_sample(dec, attach, lengths, n, rng=None, site=0, u=None, want_logp=Tr
     dt, dec_c = _C.in_dtype(dec)
     _, att_c = _C.in_dtype(attach)
     lengths = _lengths(lengths, B, dec.device)
-    if (rng is None) == (u is None):
-        raise ValueError("dmv1o_sample: pass exactly one of rng and u")
-    if u is not None:
-        if tuple(u.shape) != (n, B, 3, N, N) or u.dtype != torch.float32 or u.device != dec.device:
-            raise ValueError(f"dmv1o_sample: u must be float32 [n,B,3,N,N] = {(n, B, 3, N, N)} on {dec.device}")
-        u = u.contiguous()
-    heads = torch.empty((n, B, N), dtype=torch.int64, device=dec.device)
-    logp = torch.empty((n, B), dtype=torch.float32, device=dec.device) if want_logp else None
-    logZ = torch.empty(B, dtype=torch.float32, device=dec.device)
+    heads, logp, logZ, u, args = _sample_frame("dmv1o_sample", dec.device, B, N, n, rng, site, u, want_logp)
     L = _C.lib()
     nb = L.vlg_dmv1o_sample_workspace(B, N, n)
     ws = torch.empty(nb, dtype=torch.uint8, device=dec.device) if nb else None
-    _C.check(L.vlg_dmv1o_sample(_C.ptr(dec_c), _C.ptr(att_c), _C.ptr(lengths), B, N, dt, n, None if rng is None else _C.ptr(rng.state),
-                                int(site), _C.ptr(u), _C.ptr(heads), _C.ptr(logp), _C.ptr(logZ), _C.ptr(ws), nb, _C.stream_of(dec)),
+    _C.check(L.vlg_dmv1o_sample(_C.ptr(dec_c), _C.ptr(att_c), _C.ptr(lengths), B, N, dt, n, *args, _C.ptr(ws), nb, _C.stream_of(dec)),
              "dmv1o_sample")
     return heads, logp, logZ
 
