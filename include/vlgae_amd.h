@@ -148,6 +148,37 @@ int vlg_deptree_kbest(const void* arc, const int64_t* lengths, int B, int N, int
                       int32_t* count, void* ws, size_t ws_bytes, void* stream);
 size_t vlg_deptree_kbest_workspace(int B, int N, int K);
 
+/* The same for the valence DMV (DMV1o), which the reference cannot do (its kmax / topk stop in KMaxSemiring.sum, semirings.py:251):
+ * the K best trees of every sentence, one launch, 1 <= K <= 16.  One workgroup per sentence fills charts of K sorted values per cell
+ * and valence -- six k-way merges per span: TL and TR have operands of different valences and are not shared; both valences of an
+ * incomplete cell are T plus a staged attach + GO term, read where they are used; the complete cells are merged per valence -- then
+ * its wavefronts walk one rank each, every cell carrying its valence ("K-best trees under DMV1o").
+ *   dec [B,N,2,2,2] / attach [B,N,N,2] root-merged, in in_dtype (the inputs of vlg_dmv1o_decode), clamped as vlg_deptree_kbest clamps;
+ *   lengths [B] is required.  Natural units, additions and comparisons only: no log2 scaling.
+ *   scores [K,B] float32, non-increasing in k: the sum of the clamped input potentials along the tree (attach + dec GO per arc, dec
+ *   STOP per head, side and valence: 4 len + 1 terms), exact wherever the partial sums are representable; the scores for K are the
+ *   first K scores of any larger K.  heads [K,B,N] int64 as vlg_dmv1o_decode writes them: K different trees, also under exact ties (a
+ *   tree has one derivation).  count [B] int32 (optional): the ranks whose score is above 0.5 * -1e12; a rank at or beyond count (a
+ *   short sentence, forbidden potentials, the -1e12 vlg_dmv1o_merge writes) has score -1e12 exactly and heads 0.  An invalid length
+ *   gives count 0, heads 0 and scores NaN.
+ *   ws holds vlg_dmv1o_kbest_workspace(B, N, K) bytes (0 where the charts fit in LDS; 0 for arguments out of range).
+ *   VLG_ERR_SHAPE for N outside 2 ... 255 or K outside 1 ... 16, VLG_ERR_DTYPE, VLG_ERR_NULL for NULL dec / attach / lengths / heads /
+ *   scores, VLG_ERR_WORKSPACE; B = 0 is a no-op. */
+int vlg_dmv1o_kbest(const void* dec, const void* attach, const int64_t* lengths, int B, int N, int in_dtype, int K, int64_t* heads,
+                    float* scores, int32_t* count, void* ws, size_t ws_bytes, void* stream);
+size_t vlg_dmv1o_kbest_workspace(int B, int N, int K);
+
+/* The adjoint of those scores: cnt = sum over t < T of weight[t,b] * (derivation counts of the tree heads[t,b,:]), one launch.
+ *   heads [T,B,N] int64; lengths [B]; count [B] int32 (optional): only the trees t < count[b] are taken; weight [T,B] float32
+ *   (optional: 1).  cnt_dec [B,N,2,2,2], cnt_attach [B,N,N,2] float32, fully written.  On each side of a head the farthest child
+ *   attaches with NOCHILD and the others with HASCHILD (attach and dec GO); the STOP of a side is NOCHILD only when the side has no
+ *   child; the root token has a right side only.  A head entry outside 0 ... len (or naming the word itself) attaches nowhere; nothing
+ *   is read or written out of range.  An invalid length gives zeros.  One workgroup per sentence, every output element owned by one
+ *   lane, trees taken in order: no atomics, bit-reproducible.
+ *   VLG_ERR_SHAPE for N outside 2 ... 255 or T < 0, VLG_ERR_NULL for NULL heads / lengths / cnt_dec / cnt_attach; B = 0 is a no-op. */
+int vlg_dmv1o_tree_counts(const int64_t* heads, const int64_t* lengths, const int32_t* count, const float* weight, int T, int B, int N,
+                          float* cnt_dec, float* cnt_attach, void* stream);
+
 /* Expectations under the projective CRF, on the device: the DepTree inside(-outside) pass in dual numbers, one launch.  Every chart
  * cell carries its derivative along the direction d = v - v_sub in potential space (rule: DESIGN.md section 2, "Expectations").
  *   arc [B,N,N] in in_dtype; v, v_sub [B,N,N] in v_dtype (VLG_F32 / VLG_BF16), each optional: NULL reads as 0.  d is forced to 0 where
@@ -816,7 +847,7 @@ int vlg_selftest_xlane(int* scratch, void* stream);
 /* Thread-local message for the last non-zero return on this thread ("" if none). */
 const char* vlg_last_error(void);
 
-/* Library / ABI version, e.g. 142 = 0.1.4.2 (145: vlg_deptree_sample, vlg_deptree_sample_blocks and VLG_ERR_NULL added under the same number -- no existing argument list changed; 145: vlg_adam_clip_plan / _workspace / _step added under the same number -- no existing argument list changed; 145: vlg_eval_metrics, vlg_eval_metrics_workspace and vlg_deptree_mbr_decode added later under the same number -- no existing argument list changed; 145: vlg_step_batch_prepare and vlg_grounding_loss_ntok added; round 6, 142: vlg_attn_fuse / vlg_attn_fuse_backward take key_chunk and a workspace -- the key-split form for the
+/* Library / ABI version, e.g. 142 = 0.1.4.2 (145: vlg_dmv1o_kbest, vlg_dmv1o_kbest_workspace and vlg_dmv1o_tree_counts added under the same number -- no existing argument list changed; 145: vlg_deptree_sample, vlg_deptree_sample_blocks and VLG_ERR_NULL added under the same number -- no existing argument list changed; 145: vlg_adam_clip_plan / _workspace / _step added under the same number -- no existing argument list changed; 145: vlg_eval_metrics, vlg_eval_metrics_workspace and vlg_deptree_mbr_decode added later under the same number -- no existing argument list changed; 145: vlg_step_batch_prepare and vlg_grounding_loss_ntok added; round 6, 142: vlg_attn_fuse / vlg_attn_fuse_backward take key_chunk and a workspace -- the key-split form for the
  * shipped 1369-key factor layout -- and the gradients' storage type; vlg_attn_fuse_workspace added; round 5, 141: vlg_dropout, vlg_rng_advance, vlg_vis_encoder(_backward) added, vlg_linear_wgrad takes ld_dw and in_dtype;
  * the Python binding refuses a library whose version differs from the one it was written against; round 4: vlg_langfeat_* take the activations' storage type and the SharedDropout masks,
  * vlg_langfeat_rowscale, vlg_ff_* added, vlg_ndmv_potentials* take row strides and the gradients' storage type; round 3, 120: vlg_linear_wgrad, vlg_langfeat_*, vlg_ndmv_potentials*, vlg_dmv1o_viterbi added;

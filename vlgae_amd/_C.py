@@ -70,6 +70,9 @@ SIGNATURES = {
     "vlg_dmv1o_sample_lds_bytes": (_sz, [_i]),
     "vlg_deptree_kbest": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vlg_deptree_kbest_workspace": (_sz, [_i, _i, _i]),
+    "vlg_dmv1o_kbest": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "vlg_dmv1o_kbest_workspace": (_sz, [_i, _i, _i]),
+    "vlg_dmv1o_tree_counts": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "vlg_deptree_expect": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vlg_dmv1o_expect": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vlg_dmv1o_expect_workspace": (_sz, [_i, _i, _i]),

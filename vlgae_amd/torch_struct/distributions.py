@@ -21,7 +21,7 @@ def _out_of_scope(name):
         f"StructDistribution.{name}: no caller in VLGAE uses it (only partition / max / argmax / marginals are "
         "reached; SURVEY.md section 2) -- outside the MI355X hot path this package implements.  (Drawing trees is "
         "implemented for DependencyCRF as `sample_heads` / `heads_to_parts` and for DMV1o as `sample_heads` / `log_prob_heads`; entropy, cross-entropy, KL and expected scores as "
-        "`tree_entropy` / `tree_cross_entropy` / `tree_kl` / `expected_score` on DependencyCRF and, for the DMV, on DMV1oExpect; the k best trees as `kbest_heads` / `kbest_scores`.)")
+        "`tree_entropy` / `tree_cross_entropy` / `tree_kl` / `expected_score` on DependencyCRF and, for the DMV, on DMV1oExpect; the k best trees as `kbest_heads` / `kbest_scores` on DependencyCRF and on DMV1o.)")
 
 
 class StructDistribution(Distribution):
@@ -175,6 +175,24 @@ class DMV1o(StructDistribution):
         counts minus the expected counts -- the score-function estimator's term for trees drawn by `sample_heads`."""
         dec, attach = self.log_potentials
         return F.dmv1o_log_prob_heads(dec, attach, self.lengths, heads)
+
+    # -- k-best trees (extension: one launch, functional.dmv1o_kbest).  The reference's `kmax(k)` / `topk(k)` cannot run on a DMV1o at all
+    # (KMaxSemiring.sum has no reduction over dimension -2, semirings.py:251) and stay out of scope under those names.
+    def kbest_heads(self, k, return_scores=False):
+        """The k best trees (1 <= k <= 16) as heads [k,B,N] int64 on the device: k different trees per sentence, also under exact
+        ties, best first -- n-best parses for reranking, oracle attachment scores, a look at how peaked the posterior is.
+        return_scores=True: (heads, scores [k,B] float32, count [B] int32) -- a sentence with fewer than k trees has count < k, and
+        its ranks at or beyond count hold score NEGINF and heads 0.  Row 0 is `argmax_heads` wherever the best tree is unique."""
+        dec, attach = self.log_potentials
+        heads, scores, count = F.dmv1o_kbest(dec, attach, self.lengths, k)
+        return (heads, scores, count) if return_scores else heads
+
+    def kbest_scores(self, k):
+        """Scores [k,B] of the k best trees, non-increasing in k (NEGINF where the rank does not exist); scores[0] is `max` up to the
+        rounding of its log2-unit arithmetic.  Differentiable once with respect to both potentials: the gradient of scores[k,b] is
+        tree (k,b)'s derivation counts (every attachment with its valence and GO decision, every STOP)."""
+        dec, attach = self.log_potentials
+        return F.dmv1o_kbest_scores(dec, attach, self.lengths, k)[0]
 
     @staticmethod
     def merge(dec: Tensor, attach: Tensor, root: Tensor, one=0, zero=NEGINF):

@@ -388,6 +388,89 @@ def deptree_kbest_scores(arc, lengths, k):
     return _DepTreeKBestScores.apply(arc, lengths, k)
 
 
+_DMV_KBEST_WS_BYTES = {}
+
+
+def dmv1o_kbest(dec, attach, lengths, k):
+    """The k best projective single-root trees of the DMV of root-merged potentials dec [B,N,2,2,2] / attach [B,N,N,2], 1 <= k <= 16,
+    in ONE launch (vlg_dmv1o_kbest): (heads [k,B,N] int64 as dmv1o_decode writes them, scores [k,B] float32 non-increasing in k,
+    count [B] int32).  A rank at or beyond count[b] does not exist (short sentence, forbidden potentials): score NEGINF, heads 0.
+    No host synchronisation."""
+    _C.require_gpu(dec, "dmv1o_kbest")
+    if dec.dim() != 5 or tuple(dec.shape[2:]) != (2, 2, 2):
+        raise ValueError(f"dec must be [B,N,2,2,2], got {tuple(dec.shape)}")
+    B, N = dec.shape[:2]
+    if tuple(attach.shape) != (B, N, N, 2):
+        raise ValueError(f"attach must be [B,N,N,2] = {(B, N, N, 2)}, got {tuple(attach.shape)}")
+    k = int(k)
+    if dec.dtype != attach.dtype:
+        attach = attach.to(dec.dtype)
+    dt, dec_c = _C.in_dtype(dec)
+    _, att_c = _C.in_dtype(attach)
+    lengths = _lengths(lengths, B, dec.device)
+    heads = torch.empty((k, B, N), dtype=torch.int64, device=dec.device)
+    scores = torch.empty((k, B), dtype=torch.float32, device=dec.device)
+    count = torch.empty(B, dtype=torch.int32, device=dec.device)
+    L = _C.lib()
+    nb = _DMV_KBEST_WS_BYTES.get((B, N, k))
+    if nb is None:
+        nb = _DMV_KBEST_WS_BYTES[(B, N, k)] = L.vlg_dmv1o_kbest_workspace(B, N, k)
+    ws = torch.empty(nb, dtype=torch.uint8, device=dec.device) if nb else None
+    _C.check(L.vlg_dmv1o_kbest(_C.ptr(dec_c), _C.ptr(att_c), _C.ptr(lengths), B, N, dt, k, _C.ptr(heads), _C.ptr(scores), _C.ptr(count),
+                               _C.ptr(ws), nb, _C.stream_of(dec)), "dmv1o_kbest")
+    return heads, scores, count
+
+
+def dmv1o_tree_counts(heads, lengths, count=None, weight=None):
+    """sum_t weight[t,b] * (derivation counts of the tree heads[t,b,:]) in ONE launch (vlg_dmv1o_tree_counts): heads [T,B,N] int64,
+    count [B] int32 or None (only the trees t < count[b]), weight [T,B] float32 or None (1) -> (cnt_dec [B,N,2,2,2], cnt_attach
+    [B,N,N,2]) float32.  No atomics: bit-reproducible."""
+    _C.require_gpu(heads, "dmv1o_tree_counts")
+    if heads.dim() != 3 or heads.dtype != torch.int64:
+        raise ValueError(f"heads must be int64 [T,B,N], got {heads.dtype} {tuple(heads.shape)}")
+    T, B, N = heads.shape
+    heads = heads.contiguous()
+    lengths = _lengths(lengths, B, heads.device)
+    if count is not None:
+        if count.dtype != torch.int32 or tuple(count.shape) != (B,) or count.device != heads.device:
+            raise ValueError(f"count must be int32 [{B}] on {heads.device}")
+        count = count.contiguous()
+    if weight is not None:
+        if tuple(weight.shape) != (T, B) or weight.device != heads.device:
+            raise ValueError(f"weight must be [T,B] = {(T, B)} on {heads.device}")
+        weight = weight.to(torch.float32).contiguous()
+    cnt_dec = torch.empty((B, N, 2, 2, 2), dtype=torch.float32, device=heads.device)
+    cnt_attach = torch.empty((B, N, N, 2), dtype=torch.float32, device=heads.device)
+    _C.check(_C.lib().vlg_dmv1o_tree_counts(_C.ptr(heads), _C.ptr(lengths), _C.ptr(count), _C.ptr(weight), T, B, N, _C.ptr(cnt_dec),
+                                            _C.ptr(cnt_attach), _C.stream_of(heads)), "dmv1o_tree_counts")
+    return cnt_dec, cnt_attach
+
+
+class _DMV1oKBestScores(torch.autograd.Function):
+    """scores [k,B] of the k best trees; d scores[k,b] / d (dec, attach)[b] = the derivation counts of tree (k,b), for the ranks that
+    exist: the backward is one vlg_dmv1o_tree_counts launch weighted by the upstream gradient."""
+
+    @staticmethod
+    def forward(ctx, dec, attach, lengths, k):
+        heads, scores, count = dmv1o_kbest(dec.detach(), attach.detach(), lengths, k)
+        ctx.save_for_backward(heads, count)
+        ctx.dtypes, ctx.lengths = (dec.dtype, attach.dtype), lengths
+        ctx.mark_non_differentiable(heads, count)
+        return scores, heads, count
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_scores, _gh, _gc):
+        heads, count = ctx.saved_tensors
+        gdec, gatt = dmv1o_tree_counts(heads, ctx.lengths, count, grad_scores)
+        return gdec.to(ctx.dtypes[0]), gatt.to(ctx.dtypes[1]), None, None
+
+
+def dmv1o_kbest_scores(dec, attach, lengths, k):
+    "(scores [k,B] differentiable once in dec and attach, heads [k,B,N], count [B])"
+    return _DMV1oKBestScores.apply(dec, attach, lengths, k)
+
+
 def deptree_mbr_decode(marginals, lengths=None):
     """The MBR decode of src/model/ldndmv.py:294-299 from the DMV1o arc marginals [B,N,N,2] (float32: `grad_attach` of the Log
     semiring's inside-outside pass): `DependencyCRF(marginals.sum(-1)).argmax` as (best_score [B], heads [B,N] int64) in ONE DepTree
