@@ -195,6 +195,44 @@ int vlg_dmv1o_tree_counts(const int64_t* heads, const int64_t* lengths, const in
 int vlg_deptree_expect(const void* arc, const void* v, const void* v_sub, const int64_t* lengths, int B, int N, int in_dtype, int v_dtype,
                        float* logZ, float* ev, float* mu, float* hv, void* ws, size_t ws_bytes, void* stream);
 
+/* Labeled arc potentials phi [B,N,N,L] (head x child x label, contiguous, in_dtype, 1 <= L <= 255) around the DepTree DP -- the
+ * reference's second event shape (deptree.py:19,33-41).  The DP itself reads arc scores [B,N,N]; these three entries are the streaming
+ * work around it, one pass over phi each, no atomics (layout and lane-group table: DESIGN.md section 2, "Labeled potentials").
+ * A label takes part iff it is above the DP's clamp floor (-1e30; -inf and NaN do not): the others have probability 0.  The cells the
+ * DP never reads -- child 0, head = child, head or child beyond lengths[b] (NULL = N - 1), every cell of an invalid length -- are not
+ * loaded: whatever they hold has no effect.
+ *
+ * vlg_label_fold: arc [B,N,N] float32 = logsumexp_l phi (VLG_SEMIRING_LOG) / max_l phi (VLG_SEMIRING_MAX); VLG_NEGINF (-1e12) in the
+ *   never-read cells, -inf where no label takes part.  best [B,N,N] uint8 (optional) = the lowest label attaining the maximum (0 in the
+ *   never-read cells and where no label takes part).  dbar [B,N,N] float32 (optional, Log only) = sum_l p_l (v_l - v_sub_l) with
+ *   p_l = exp(phi_l - arc): the dual part of the fold along the direction v - v_sub, [B,N,N,L] each in v_dtype, each optional (NULL
+ *   reads as 0), forced to 0 where the label takes no part; 0 in the never-read cells.  v == v_sub == phi gives dbar = 0 exactly.
+ * vlg_label_expand: out [B,N,N,L] in out_dtype (VLG_F32 or in_dtype), fully written:
+ *     mode 0:  out_l = scale[b] p_l (g1 + g2 (d_l - dbar))      mode 1:  out_l = scale[b] g1 p_l
+ *   p_l = exp(phi_l - arc) (Log) or [l == best] (Max: best required); arc, best, dbar as the fold wrote them; g1 [B,N,N] float32;
+ *   g2, dbar, v, v_sub optional (NULL = 0); scale [B] float32 read at b * scale_stride (stride 0: one scalar), NULL = 1.  0 in the
+ *   never-read cells and in rows where no label takes part.  With the arc-level mu / hv of vlg_deptree_expect run on (arc, dbar):
+ *     d E[<c,tree>] / d phi = p (hv + mu (c - cbar))   d / d c = mu p   (mode 1)      d H / d phi = -p (hv + mu (phi - phibar))
+ *     d H[p,q] / d phi_p = d KL / d phi_p = -p (hv + mu_p (d - dbar))      d / d phi_q = mu_q q - mu_p p   (two mode-1 calls)
+ * vlg_label_draw: labels [S,B,N] int64 for the heads [S,B,N] the tree sampler wrote: word c draws from softmax_l phi[b, heads[c], c, :]
+ *   by the sampler's rule (first label whose running weight sum exceeds u total) under u_label[s,b,c] (float32 [S,B,N]) or the sampler's
+ *   counter with draw kind 3: Philox counter (3 << 16 | head << 8 | child, sample, sentence, step), key as vlg_deptree_sample's -- pass
+ *   the rng and site of the tree draw.  Exactly one of rng / u_label.  0 at c = 0, in padding and for a tree the sampler gave up on
+ *   (heads 0 throughout).  logp [S,B] (optional, needs arc = the Log fold's): += sum_c (phi_label - arc): the sampler's log-probability
+ *   of the tree becomes that of the labeled tree.
+ * vlg_label_lanes: the plan of fold / expand when every buffer is 16-byte aligned (a buffer that is not takes the element image): lanes per row | 0x100 for the vector image; 0 if out of range.
+ *   VLG_ERR_SHAPE for N outside 2 ... 255, L outside 1 ... 255, S < 1 or a grid beyond 2^24 - 1 workgroups of 256 lanes (B x ceil(N N G / 256) for fold / expand, ceil(S B / 4) for draw); VLG_ERR_DTYPE; VLG_ERR_ARG
+ *   for a missing buffer, dbar or a missing best under the wrong semiring, v_sub without v, a mode or stride out of range, both or
+ *   neither of rng / u_label; B = 0 is a no-op. */
+int vlg_label_fold(const void* phi, const void* v, const void* v_sub, const int64_t* lengths, int B, int N, int L, int in_dtype, int v_dtype,
+                   int semiring, float* arc, unsigned char* best, float* dbar, void* stream);
+int vlg_label_expand(const void* phi, const void* v, const void* v_sub, const int64_t* lengths, int B, int N, int L, int in_dtype, int v_dtype,
+                     int out_dtype, int semiring, int mode, const float* arc, const unsigned char* best, const float* g1, const float* g2,
+                     const float* dbar, const float* scale, int scale_stride, void* out, void* stream);
+int vlg_label_draw(const void* phi, const float* arc, const int64_t* heads, const int64_t* lengths, int B, int N, int L, int S, int in_dtype,
+                   const uint64_t* rng, unsigned site, const float* u_label, int64_t* labels, float* logp, void* stream);
+int vlg_label_lanes(int L, int in_dtype);
+
 /* The same for the valence DMV (DMV1o): its inside(-outside) pass in dual numbers, one launch (rule: DESIGN.md section 2,
  * "Expectations under DMV1o").  The direction is d = (v_dec - v_sub_dec, v_attach - v_sub_attach).
  *   dec [B,N,2,2,2], attach [B,N,N,2] root-merged potentials in in_dtype; lengths [B] int64.  v_dec, v_sub_dec are dec-shaped and
@@ -847,7 +885,7 @@ int vlg_selftest_xlane(int* scratch, void* stream);
 /* Thread-local message for the last non-zero return on this thread ("" if none). */
 const char* vlg_last_error(void);
 
-/* Library / ABI version, e.g. 142 = 0.1.4.2 (145: vlg_dmv1o_kbest, vlg_dmv1o_kbest_workspace and vlg_dmv1o_tree_counts added under the same number -- no existing argument list changed; 145: vlg_deptree_sample, vlg_deptree_sample_blocks and VLG_ERR_NULL added under the same number -- no existing argument list changed; 145: vlg_adam_clip_plan / _workspace / _step added under the same number -- no existing argument list changed; 145: vlg_eval_metrics, vlg_eval_metrics_workspace and vlg_deptree_mbr_decode added later under the same number -- no existing argument list changed; 145: vlg_step_batch_prepare and vlg_grounding_loss_ntok added; round 6, 142: vlg_attn_fuse / vlg_attn_fuse_backward take key_chunk and a workspace -- the key-split form for the
+/* Library / ABI version, e.g. 142 = 0.1.4.2 (145: vlg_label_fold, vlg_label_expand, vlg_label_draw and vlg_label_lanes added under the same number -- no existing argument list changed; 145: vlg_dmv1o_kbest, vlg_dmv1o_kbest_workspace and vlg_dmv1o_tree_counts added under the same number -- no existing argument list changed; 145: vlg_deptree_sample, vlg_deptree_sample_blocks and VLG_ERR_NULL added under the same number -- no existing argument list changed; 145: vlg_adam_clip_plan / _workspace / _step added under the same number -- no existing argument list changed; 145: vlg_eval_metrics, vlg_eval_metrics_workspace and vlg_deptree_mbr_decode added later under the same number -- no existing argument list changed; 145: vlg_step_batch_prepare and vlg_grounding_loss_ntok added; round 6, 142: vlg_attn_fuse / vlg_attn_fuse_backward take key_chunk and a workspace -- the key-split form for the
  * shipped 1369-key factor layout -- and the gradients' storage type; vlg_attn_fuse_workspace added; round 5, 141: vlg_dropout, vlg_rng_advance, vlg_vis_encoder(_backward) added, vlg_linear_wgrad takes ld_dw and in_dtype;
  * the Python binding refuses a library whose version differs from the one it was written against; round 4: vlg_langfeat_* take the activations' storage type and the SharedDropout masks,
  * vlg_langfeat_rowscale, vlg_ff_* added, vlg_ndmv_potentials* take row strides and the gradients' storage type; round 3, 120: vlg_linear_wgrad, vlg_langfeat_*, vlg_ndmv_potentials*, vlg_dmv1o_viterbi added;

@@ -74,6 +74,10 @@ SIGNATURES = {
     "vlg_dmv1o_kbest_workspace": (_sz, [_i, _i, _i]),
     "vlg_dmv1o_tree_counts": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "vlg_deptree_expect": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "vlg_label_fold": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "vlg_label_expand": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "vlg_label_draw": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, ctypes.c_uint, _vp, _vp, _vp, _vp]),
+    "vlg_label_lanes": (_i, [_i, _i]),
     "vlg_dmv1o_expect": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vlg_dmv1o_expect_workspace": (_sz, [_i, _i, _i]),
     "vlg_eval_metrics_workspace": (_sz, [_i]),

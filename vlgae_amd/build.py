@@ -30,8 +30,9 @@ DP_INST += (("vlg_dp_inst.hip", "vlg_dp_inst_212", DP_FLAGS + ("-DVLG_INST_FAMIL
 # vlg_sample.hip (tree sampling) runs the same inside pass but compares against a uniform that may be NaN: no -ffinite-math-only;
 # nor for vlg_expect.hip (dual-number DepTree pass), whose direction may hold anything where an arc is forbidden and is discarded by a select;
 # vlg_kbest.hip (k-best trees) only adds and compares: plain flags; vlg_dmv_sample.hip (DMV1o tree sampling) as vlg_sample.hip;
-# vlg_dmv_expect.hip (dual-number DMV1o pass) as vlg_expect.hip; vlg_dmv_kbest.hip (k-best DMV1o trees, tree counts) as vlg_kbest.hip
-UNITS = DP_INST + (("vlg_dp.hip", "vlg_dp", DP_FLAGS), ("vlg_dp_pair.hip", "vlg_dp_pair", DP_FLAGS), ("vlg_sample.hip", "vlg_sample", ()), ("vlg_dmv_sample.hip", "vlg_dmv_sample", ()), ("vlg_expect.hip", "vlg_expect", ()), ("vlg_dmv_expect.hip", "vlg_dmv_expect", ()), ("vlg_kbest.hip", "vlg_kbest", ()), ("vlg_dmv_kbest.hip", "vlg_dmv_kbest", ())) + tuple(
+# vlg_dmv_expect.hip (dual-number DMV1o pass) as vlg_expect.hip; vlg_dmv_kbest.hip (k-best DMV1o trees, tree counts) as vlg_kbest.hip;
+# vlg_label.hip (labeled potentials: fold / expand / draw) computes with -inf (a label of probability 0): plain flags
+UNITS = DP_INST + (("vlg_dp.hip", "vlg_dp", DP_FLAGS), ("vlg_dp_pair.hip", "vlg_dp_pair", DP_FLAGS), ("vlg_sample.hip", "vlg_sample", ()), ("vlg_dmv_sample.hip", "vlg_dmv_sample", ()), ("vlg_expect.hip", "vlg_expect", ()), ("vlg_dmv_expect.hip", "vlg_dmv_expect", ()), ("vlg_kbest.hip", "vlg_kbest", ()), ("vlg_dmv_kbest.hip", "vlg_dmv_kbest", ()), ("vlg_label.hip", "vlg_label", ())) + tuple(
     (src, os.path.splitext(src)[0], ()) for src in
     ("vlg_align.hip", "vlg_attn.hip", "vlg_ground.hip", "vlg_decode.hip", "vlg_arc.hip", "vlg_rel.hip", "vlg_gemm.hip", "vlg_langfeat.hip", "vlg_ff.hip", "vlg_ffgemm.hip", "vlg_encoders.hip", "vlg_scorer.hip", "vlg_batch.hip", "vlg_rules1o.hip", "vlg_eval.hip", "vlg_optim.hip", "vlg_feed.cpp", "vlg_capi.cpp"))
 SOURCES = tuple(sorted({u[0] for u in UNITS}))

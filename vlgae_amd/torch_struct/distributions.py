@@ -21,7 +21,9 @@ def _out_of_scope(name):
         f"StructDistribution.{name}: no caller in VLGAE uses it (only partition / max / argmax / marginals are "
         "reached; SURVEY.md section 2) -- outside the MI355X hot path this package implements.  (Drawing trees is "
         "implemented for DependencyCRF as `sample_heads` / `heads_to_parts` and for DMV1o as `sample_heads` / `log_prob_heads`; entropy, cross-entropy, KL and expected scores as "
-        "`tree_entropy` / `tree_cross_entropy` / `tree_kl` / `expected_score` on DependencyCRF and, for the DMV, on DMV1oExpect; the k best trees as `kbest_heads` / `kbest_scores` on DependencyCRF and on DMV1o.)")
+        "`tree_entropy` / `tree_cross_entropy` / `tree_kl` / `expected_score` on DependencyCRF and, for the DMV, on DMV1oExpect; the k best trees as `kbest_heads` / `kbest_scores` on DependencyCRF and on DMV1o.  "
+        "A DependencyCRF on labeled potentials [B,N,N,L] has all of these except the k best trees, and `argmax_labels` / "
+        "`sample_heads(return_labels=True)` for the labels.)")
 
 
 class StructDistribution(Distribution):
@@ -272,44 +274,88 @@ class DependencyCRF(StructDistribution):
 
     log_potentials [B,N,N] head -> child with the root at index 0; lengths [B] or None (= N-1).
     partition / max: [B].  argmax / marginals: [B,N,N].
+
+    Labeled: log_potentials [B,N,N,L] head x child x label, 1 <= L <= 255 (deptree.py:19,33-41: the label axis is summed in the
+    semiring in front of the DP).  partition / max: [B].  argmax / marginals: [B,N,N,L].  Every extension below takes the labeled
+    shape too, except the k best trees; `argmax_labels` and `sample_heads(return_labels=True)` give the labels.
     """
 
     def __init__(self, log_potentials, lengths=None, args={}, multiroot=False):
         super().__init__(log_potentials, lengths, args)
         assert not multiroot, "multiroot is asserted False by the reference's DP (deptree.py:26-27)"
         self.multiroot = multiroot
+        self.labeled = log_potentials.dim() == 4
 
     def _sum(self, semiring):
+        if self.labeled:
+            return F.deptree_labeled_sum(self.log_potentials, self.lengths, semiring.kernel_id)
         return F.deptree_sum(self.log_potentials, self.lengths, semiring.kernel_id)
 
     def _marginals(self, semiring):
         arc = self.log_potentials
-        _, garc = F.deptree_run(arc, self.lengths, semiring.kernel_id, True)
+        if self.labeled:
+            garc = F.deptree_labeled_marginals(arc, self.lengths, semiring.kernel_id)
+        else:
+            _, garc = F.deptree_run(arc, self.lengths, semiring.kernel_id, True)
         return garc.to(arc.dtype) if arc.dtype == torch.float64 else garc
+
+    @lazy_property
+    def _labeled_decode(self):
+        return F.deptree_labeled_decode(self.log_potentials, self.lengths)
 
     @lazy_property
     def argmax_heads(self):
         "Extension: best tree as heads [B,N] on the device (see DMV1o.argmax_heads; MBR decode of ldndmv.py:294-303)."
+        if self.labeled:
+            return self._labeled_decode[1]
         return F.deptree_decode(self.log_potentials, self.lengths)[1]
 
-    def sample_heads(self, n, rng=None, u=None, return_log_prob=False):
+    @lazy_property
+    def argmax_labels(self):
+        """Extension, labeled potentials only: the labels of the best labeled tree, [B,N] int64 on the device -- labels[b,c] is the
+        label of the arc `argmax_heads[b,c]` -> c, 0 at c = 0 and in padding.  No host synchronisation."""
+        if not self.labeled:
+            raise ValueError("argmax_labels: the potentials are unlabeled ([B,N,N]); labeled potentials are [B,N,N,L]")
+        return self._labeled_decode[2]
+
+    def _no_labeled_kbest(self):
+        raise NotImplementedError(
+            "DependencyCRF.kbest_heads / kbest_scores on labeled potentials [B,N,N,L]: the k best *labeled* trees need a K-list of "
+            "(score, label) per arc inside the k-best chart (two trees of one shape may differ in a label only), and that chart is not "
+            "built.  `kbest_heads` on `potentials.logsumexp(-1)` or `.max(-1).values` ranks the unlabeled trees.")
+
+    def sample_heads(self, n, rng=None, u=None, return_log_prob=False, return_labels=False, u_label=None):
         """Extension (not in the reference): n trees per sentence drawn from the distribution, as heads [n,B,N] int64 on the device
         (heads[s,b,c] = head of word c, 0 for c = 0 and padding) -- one kernel launch, no host synchronisation.  `rng`: an
         `encoders.DeviceRng` whose (seed, step) keys the draws (the same state gives the same trees; the caller advances it);
         `u`: explicit uniforms [n,B,3,N,N] instead.  With neither, the distribution creates and keeps a DeviceRng seeded from
         `torch.initial_seed()` and advances it after each call.  return_log_prob=True: (heads, log_prob [n,B]).
         The reference's `sample(sample_shape)` (distributions.py:195-217) stays out of scope under that name -- it raises, as every
-        other unreached method does; `DependencyCRF.heads_to_parts(dist.sample_heads(n))` is its event format."""
+        other unreached method does; `DependencyCRF.heads_to_parts(dist.sample_heads(n))` is its event format.
+        Labeled potentials: the tree is drawn from the label-summed arc scores and, with return_labels=True, every arc's label from
+        the softmax over its labels: (heads, labels [n,B,N] int64[, log_prob]) -- labels 0 at c = 0 and in padding; log_prob is then
+        the labeled tree's.  Explicit uniforms come as the pair `u`, `u_label` [n,B,N]."""
+        if (return_labels or u_label is not None) and not self.labeled:
+            raise ValueError("sample_heads: labels need labeled potentials [B,N,N,L]")
+        if u_label is not None and not return_labels:
+            raise ValueError("sample_heads: u_label draws the labels; pass return_labels=True with it")
         own = rng is None and u is None
         if own:
             if getattr(self, "_sample_rng", None) is None:
                 from ..encoders import DeviceRng
                 self._sample_rng = DeviceRng(torch.initial_seed() & 0x7FFFFFFFFFFFFFFF, self.log_potentials.device)
             rng = self._sample_rng
-        heads, logp, _ = F.deptree_sample(self.log_potentials, self.lengths, n, rng=rng, u=u, want_logp=return_log_prob)
+        if self.labeled and return_labels:
+            heads, labels, logp, _ = F.deptree_labeled_sample(self.log_potentials, self.lengths, n, rng=rng, u=u, u_label=u_label,
+                                                              want_logp=return_log_prob)
+        else:   # (labeled without labels: the marginal over the labels is the tree distribution of the folded arc scores)
+            arc = F.label_fold(self.log_potentials.detach(), self.lengths, 0)[0] if self.labeled else self.log_potentials
+            heads, logp, _ = F.deptree_sample(arc, self.lengths, n, rng=rng, u=u, want_logp=return_log_prob)
         if own:
             rng.advance()
-        return (heads, logp) if return_log_prob else heads
+        out = (heads, labels) if return_labels else (heads,)
+        out = out + (logp,) if return_log_prob else out
+        return out if len(out) > 1 else out[0]
 
     # -- k-best trees (extension: one launch, functional.deptree_kbest).  The reference's `kmax(k)` / `topk(k)` (distributions.py:135-156)
     # stay out of scope under those names, as `sample` does next to `sample_heads`.
@@ -318,38 +364,57 @@ class DependencyCRF(StructDistribution):
         ties, best first; `DependencyCRF.heads_to_parts(dist.kbest_heads(k), lengths)` is the event format of the reference's
         `topk(k)`.  return_scores=True: (heads, scores [k,B] float32, count [B] int32) -- a sentence with fewer than k trees has
         count < k, and its ranks at or beyond count hold score NEGINF and heads 0."""
+        if self.labeled:
+            self._no_labeled_kbest()
         heads, scores, count = F.deptree_kbest(self.log_potentials, self.lengths, k)
         return (heads, scores, count) if return_scores else heads
 
     def kbest_scores(self, k):
         """Scores [k,B] of the k best trees, non-increasing in k: the reference's `kmax(k)` wherever the rank exists (NEGINF where it
         does not).  Differentiable once with respect to the potentials: the gradient of scores[k,b] is tree (k,b)'s arc indicators."""
+        if self.labeled:
+            self._no_labeled_kbest()
         return F.deptree_kbest_scores(self.log_potentials, self.lengths, k)[0]
 
     # -- expectations (extension: one dual-number inside-outside launch each, exact gradients; functional.deptree_expect) ------------
     # The reference's names (`entropy`, `cross_entropy`, `kl`, `risk`, distributions.py:79-114) stay out of scope under those names,
     # as `sample` does next to `sample_heads`.  All return [B] and are differentiable once with respect to every potential.
     def expected_score(self, cost):
-        "E_p[<cost, tree>] for arc costs [B,N,N]: the reference's `risk(cost)`."
+        "E_p[<cost, tree>] for arc costs [B,N,N] (labeled: [B,N,N,L]): the reference's `risk(cost)`."
+        if self.labeled:
+            return F.deptree_labeled_expected_score(self.log_potentials, self.lengths, cost)
         return F.deptree_expected_score(self.log_potentials, self.lengths, cost)
 
     def tree_entropy(self):
         "H[p]: the reference's `entropy`."
+        if self.labeled:
+            return F.deptree_labeled_entropy(self.log_potentials, self.lengths)
         return F.deptree_entropy(self.log_potentials, self.lengths)
 
     def tree_cross_entropy(self, other):
         "H[p, q] with q = `other` (a DependencyCRF over the same sentences): the reference's `cross_entropy(other)`."
+        if self.labeled:
+            return F.deptree_labeled_cross_entropy(self.log_potentials, other.log_potentials, self.lengths)
         return F.deptree_cross_entropy(self.log_potentials, other.log_potentials, self.lengths)
 
     def tree_kl(self, other):
         "KL[p || q] = H[p, q] - H[p]; exactly 0 with zero gradients when both hold the same potentials."
+        if self.labeled:
+            return F.deptree_labeled_kl(self.log_potentials, other.log_potentials, self.lengths)
         return F.deptree_kl(self.log_potentials, other.log_potentials, self.lengths)
 
     @staticmethod
-    def heads_to_parts(heads, lengths=None):
+    def heads_to_parts(heads, lengths=None, labels=None, num_labels=None):
         """Extension: head vectors [..., B, N] -> 0/1 float32 arc indicators [..., B, N, N] (parts[..., h, c] = 1 iff h is the head of
         word c, 1 <= c <= length; lengths None = N - 1) on the heads' device: the event format of the reference's `sample` /
-        `to_parts` (deptree.py:163-186), which `log_prob` accepts."""
+        `to_parts` (deptree.py:163-186), which `log_prob` accepts.  With `labels` [..., B, N] (and num_labels = L, which no device
+        tensor can tell without a host synchronisation): [..., B, N, N, L], parts[..., h, c, l] = 1 iff also l is the label of word c."""
+        if labels is not None:
+            if num_labels is None:
+                raise ValueError("heads_to_parts: labels need num_labels")
+            arcs = DependencyCRF.heads_to_parts(heads, lengths)
+            hot = torch.nn.functional.one_hot(labels, int(num_labels)).to(torch.float32)   # [..., B, N(child), L]
+            return arcs.unsqueeze(-1) * hot.unsqueeze(-3)
         N = heads.shape[-1]
         pos = torch.arange(N, device=heads.device)
         if lengths is None:
@@ -362,6 +427,6 @@ class DependencyCRF(StructDistribution):
         return parts.scatter_(-2, heads.unsqueeze(-2), word.to(torch.float32).unsqueeze(-2))
 
     def log_prob(self, value):
-        "log p(tree) for 0/1 arc indicators `value` [..., B, N, N] (distributions.py:55-75)."
-        score = (self.log_potentials * value.type_as(self.log_potentials)).flatten(-2).sum(-1)
+        "log p(tree) for 0/1 arc indicators `value` [..., B, N, N] (labeled: [..., B, N, N, L]) (distributions.py:55-75)."
+        score = (self.log_potentials * value.type_as(self.log_potentials)).flatten(-3 if self.labeled else -2).sum(-1)
         return score - self.partition

@@ -81,7 +81,7 @@ def deptree_run(arc, lengths, semiring, want_grad, grad_logZ=None):
     """Raw launcher.  arc [B,N,N] -> logZ [B] (+ grad_arc fp32)."""
     _C.require_gpu(arc, "deptree")
     if arc.dim() != 3:
-        raise ValueError("potentials must have dim of 3 (unlabeled)")   # deptree.py:30-31 (labeled: out of scope)
+        raise ValueError("potentials must have dim of 3 (unlabeled)")   # deptree.py:30-31 (labeled potentials go through deptree_labeled_*, which fold them to arc scores first)
     B, N, N2 = arc.shape
     assert N == N2, "Non-square potentials"                              # deptree.py:149
     dt, arc_c = _C.in_dtype(arc)
@@ -796,6 +796,276 @@ def deptree_cross_entropy(arc_p, arc_q, lengths):
 
 def deptree_kl(arc_p, arc_q, lengths):
     return _DepTreeKL.apply(arc_p, arc_q, lengths)
+
+
+# ---- labeled arc potentials phi [B,N,N,L] (deptree.py:19,33-41) ------------------------------------------------------------------------
+# The DP reads arc scores [B,N,N]: vlg_label_fold reduces the label axis in the semiring in front of it, vlg_label_expand spreads an
+# arc-level gradient back over the labels behind it, vlg_label_draw labels the arcs of sampled trees.  One pass over phi each; no
+# [B,N,N,L] temporary besides the result.
+def _labeled_in(phi, name):
+    _C.require_gpu(phi, name)
+    if phi.dim() != 4:
+        raise ValueError("labeled potentials must have dim of 4 (head x child x label)")
+    B, N, N2, L = phi.shape
+    assert N == N2, "Non-square potentials"
+    if not 1 <= L <= 255:
+        raise ValueError(f"{name}: 1 <= L <= 255 labels (got {L})")
+    dt, phi_c = _C.in_dtype(phi)
+    return B, N, L, dt, phi_c
+
+
+def _label_dirs(name, shape, v, v_sub):
+    "(v_dtype, v, v_sub) as the kernels take them: both in one storage type (bf16 only when every one given is bf16), contiguous"
+    vs = [t for t in (v, v_sub) if t is not None]
+    for t in vs:
+        _C.require_gpu(t, name)
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name}: direction must be [B,N,N,L] = {tuple(shape)}, got {tuple(t.shape)}")
+    if v_sub is not None and v is None:
+        raise ValueError(f"{name}: v_sub without v")
+    vdt = _C.F32
+    if vs:
+        if all(t.dtype == torch.bfloat16 for t in vs):
+            vdt = _C.BF16
+        else:
+            v, v_sub = (None if t is None else (t if t.dtype == torch.float32 else t.detach().float()) for t in (v, v_sub))
+        v, v_sub = (None if t is None else (t if t.is_contiguous() else t.contiguous()) for t in (v, v_sub))
+    return vdt, v, v_sub
+
+
+def label_fold(phi, lengths, semiring, want_best=False, v=None, v_sub=None):
+    """Raw launcher of vlg_label_fold.  phi [B,N,N,L] -> (arc [B,N,N] float32 = logsumexp_l / max_l phi, best [B,N,N] uint8 = the lowest
+    label attaining the maximum or None, dbar [B,N,N] float32 = sum_l p_l (v_l - v_sub_l) or None: given iff v is)."""
+    B, N, L, dt, phi_c = _labeled_in(phi, "label_fold")
+    vdt, v, v_sub = _label_dirs("label_fold", phi.shape, v, v_sub)
+    lengths = _lengths(lengths, B, phi.device, allow_none=True)
+    (arc, dbar), _ = _C.alloc_f32(phi.device, [(B, N, N), (B, N, N) if v is not None else None])
+    best = torch.empty((B, N, N), dtype=torch.uint8, device=phi.device) if want_best else None
+    _C.check(_C.lib().vlg_label_fold(_C.ptr(phi_c), _C.ptr(v), _C.ptr(v_sub), _C.ptr(lengths), B, N, L, dt, vdt, semiring, _C.ptr(arc),
+                                     _C.ptr(best), _C.ptr(dbar), _C.stream_of(phi)), "label_fold")
+    return arc, best, dbar
+
+
+def label_expand(phi, lengths, semiring, arc, g1, best=None, g2=None, dbar=None, v=None, v_sub=None, scale=None, mode=0, out_dtype=None):
+    """Raw launcher of vlg_label_expand: out [B,N,N,L] = scale[b] p_l (g1 + g2 (v_l - v_sub_l - dbar)) (mode 0) or scale[b] g1 p_l
+    (mode 1), p_l = exp(phi_l - arc) (Log) or [l == best] (Max); arc / best / dbar as label_fold returned them, g1 / g2 [B,N,N] float32,
+    scale [B] or None.  out_dtype: float32 (default) or phi's own bfloat16."""
+    B, N, L, dt, phi_c = _labeled_in(phi, "label_expand")
+    vdt, v, v_sub = _label_dirs("label_expand", phi.shape, v, v_sub)
+    lengths = _lengths(lengths, B, phi.device, allow_none=True)
+    odt = _C.BF16 if out_dtype == torch.bfloat16 and dt == _C.BF16 else _C.F32
+    out = torch.empty((B, N, N, L), dtype=torch.bfloat16 if odt == _C.BF16 else torch.float32, device=phi.device)
+    stride = 1
+    if scale is not None:
+        scale = scale.detach()
+        if scale.dtype != torch.float32:
+            scale = scale.float()
+        if scale.numel() == 1 or scale.stride() == (0,) * scale.dim():
+            stride = 0                                                   # the expanded scalar a `.sum()` hands back
+        else:
+            scale = scale.reshape(B)
+            if not scale.is_contiguous():
+                scale = scale.contiguous()
+    _C.check(_C.lib().vlg_label_expand(_C.ptr(phi_c), _C.ptr(v), _C.ptr(v_sub), _C.ptr(lengths), B, N, L, dt, vdt, odt, semiring, mode,
+                                       _C.ptr(arc), _C.ptr(best), _C.ptr(g1), _C.ptr(g2), _C.ptr(dbar), _C.ptr(scale), stride, _C.ptr(out),
+                                       _C.stream_of(phi)), "label_expand")
+    return out
+
+
+def _expand_to(dtype, *args, **kw):
+    "label_expand in the storage type of the tensor the gradient belongs to (bf16 directly where the kernel can, else through float32)"
+    return label_expand(*args, out_dtype=dtype, **kw).to(dtype)
+
+
+class _DepTreeLabeledSum(torch.autograd.Function):
+    """semiring-sum over all labeled trees: fold, then the DP on the arc scores.  backward spreads the arc counts over the labels
+    (softmax over the labels in Log, the best label in Max) with grad_out as the scale: no [B,N,N,L] tensor exists in forward."""
+
+    @staticmethod
+    def forward(ctx, phi, lengths, semiring):
+        want = ctx.needs_input_grad[0]
+        arc, best, _ = label_fold(phi, lengths, semiring, want_best=want and semiring == _C.SEMIRING_MAX)
+        if semiring == _C.SEMIRING_MAX:
+            # The best tree's score is summed from the folded scores on its arcs, as the samplers sum a tree's score from the input
+            # potentials: the DP's own value carries the rounding of its log2-unit charts, this one is exact wherever float32 adds
+            # the scores exactly.  (An invalid length keeps the DP's NaN.)
+            logZ, garc = deptree_run(arc, lengths, semiring, True)
+            logZ = torch.where(torch.isnan(logZ), logZ, torch.where(garc > 0, arc, torch.zeros_like(arc)).sum((1, 2)))
+        else:
+            logZ, garc = deptree_run(arc, lengths, semiring, want)
+        if want:
+            ctx.save_for_backward(phi, arc, garc, best)
+        ctx.lengths, ctx.semiring = lengths, semiring
+        return logZ.to(_out_dtype(phi))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        phi, arc, garc, best = ctx.saved_tensors
+        return _expand_to(phi.dtype, phi, ctx.lengths, ctx.semiring, arc, garc, best=best, scale=grad_out), None, None
+
+
+def deptree_labeled_sum(phi, lengths, semiring):
+    return _DepTreeLabeledSum.apply(phi, lengths, semiring)
+
+
+def deptree_labeled_marginals(phi, lengths, semiring):
+    "labeled arc marginals (Log) / the best labeled tree's 0/1 parts (Max): [B,N,N,L] float32 -- fold, inside-outside, expand"
+    arc, best, _ = label_fold(phi.detach(), lengths, semiring, want_best=semiring == _C.SEMIRING_MAX)
+    _, garc = deptree_run(arc, lengths, semiring, True)
+    return label_expand(phi.detach(), lengths, semiring, arc, garc, best=best)
+
+
+def deptree_labeled_decode(phi, lengths):
+    """(best_score [B], heads [B,N], labels [B,N] int64) of the best labeled tree: labels[b,c] = the label of the arc into word c
+    (0 at c = 0 and in padding) -- `best` gathered at (heads[c], c) on the device, no host synchronisation."""
+    arc, best, _ = label_fold(phi.detach(), lengths, _C.SEMIRING_MAX, want_best=True)
+    score, heads = deptree_decode(arc, lengths)
+    B, N = heads.shape
+    labels = best.view(B, N * N).gather(1, heads * N + torch.arange(N, device=heads.device)).to(torch.int64)
+    return score, heads, labels
+
+
+def deptree_labeled_sample(phi, lengths, n, rng=None, site=0, u=None, u_label=None, want_logp=True):
+    """n labeled trees per sentence: (heads [n,B,N], labels [n,B,N] int64, logp [n,B] or None, logZ [B]).  The tree comes from
+    deptree_sample on the folded arc scores, the labels from vlg_label_draw under the same (seed, step, site) -- or, with explicit
+    uniforms, under u_label [n,B,N] float32 next to the tree sampler's u.  logp is the labeled tree's score minus logZ."""
+    B, N, L, dt, phi_c = _labeled_in(phi, "deptree_labeled_sample")
+    if (u is None) != (u_label is None):
+        raise ValueError("deptree_labeled_sample: explicit uniforms come as the pair u [n,B,3,N,N] and u_label [n,B,N]")
+    n = int(n)
+    if u_label is not None:
+        if tuple(u_label.shape) != (n, B, N) or u_label.dtype != torch.float32 or u_label.device != phi.device:
+            raise ValueError(f"deptree_labeled_sample: u_label must be float32 [n,B,N] = {(n, B, N)} on {phi.device}")
+        u_label = u_label.contiguous()
+    lengths = _lengths(lengths, B, phi.device, allow_none=True)
+    arc, _, _ = label_fold(phi_c, lengths, _C.SEMIRING_LOG)
+    heads, logp, logZ = deptree_sample(arc, lengths, n, rng=rng, site=site, u=u, want_logp=want_logp)
+    labels = torch.empty((n, B, N), dtype=torch.int64, device=phi.device)
+    _C.check(_C.lib().vlg_label_draw(_C.ptr(phi_c), _C.ptr(arc), _C.ptr(heads), _C.ptr(lengths), B, N, L, n, dt,
+                                     None if rng is None else _C.ptr(rng.state), int(site), _C.ptr(u_label), _C.ptr(labels), _C.ptr(logp),
+                                     _C.stream_of(phi)), "label_draw")
+    return heads, labels, logp, logZ
+
+
+class _DepTreeLabeledExpectedScore(torch.autograd.Function):
+    """E_p[<cost, labeled tree>]: the fold's dual part cbar is the arc-level cost; d/d phi = p (hv + mu (cost - cbar)), d/d cost = mu p."""
+
+    @staticmethod
+    def forward(ctx, phi, lengths, cost):
+        wa, wc = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
+        arc, _, dbar = label_fold(phi, lengths, _C.SEMIRING_LOG, v=cost)
+        _, ev, mu, hv = deptree_expect(arc, lengths, v=dbar, want_mu=wa or wc, want_hv=wa)
+        ctx.save_for_backward(phi, cost, arc, dbar, mu, hv)
+        ctx.lengths = lengths
+        return ev.to(_out_dtype(phi))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        phi, cost, arc, dbar, mu, hv = ctx.saved_tensors
+        ga = gc = None
+        if ctx.needs_input_grad[0]:
+            ga = _expand_to(phi.dtype, phi, ctx.lengths, _C.SEMIRING_LOG, arc, hv, g2=mu, dbar=dbar, v=cost, scale=grad_out)
+        if ctx.needs_input_grad[2]:
+            gc = _expand_to(cost.dtype, phi, ctx.lengths, _C.SEMIRING_LOG, arc, mu, scale=grad_out, mode=1)
+        return ga, None, gc
+
+
+class _DepTreeLabeledEntropy(torch.autograd.Function):
+    """H[p] = logZ - <mu, phibar>: the direction is the distribution's own potentials; d/d phi = -p (hv + mu (phi - phibar))."""
+
+    @staticmethod
+    def forward(ctx, phi, lengths):
+        want = ctx.needs_input_grad[0]
+        arc, _, dbar = label_fold(phi, lengths, _C.SEMIRING_LOG, v=phi)
+        logZ, ev, mu, hv = deptree_expect(arc, lengths, v=dbar, want_mu=want, want_hv=want)
+        if want:
+            ctx.save_for_backward(phi, arc, dbar, mu, hv)
+        ctx.lengths = lengths
+        return (logZ - ev).to(_out_dtype(phi))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        phi, arc, dbar, mu, hv = ctx.saved_tensors
+        return _expand_to(phi.dtype, phi, ctx.lengths, _C.SEMIRING_LOG, arc, hv, g2=mu, dbar=dbar, v=phi, scale=-grad_out), None
+
+
+def _labeled_pq(ctx, phi_p, phi_q, lengths, sub):
+    """What labeled cross-entropy and KL share (see _deptree_pq): p folded along v = phi_q (- phi_p when `sub`), q folded without a
+    direction; then the launches of the unlabeled path on the arc scores.  On equal potentials the two folds write the same arc scores
+    (the direction does not enter them), so the two logZ agree bit for bit and dbar, ev, hv are exactly 0."""
+    wp, wq = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    arc_p, _, dbar = label_fold(phi_p, lengths, _C.SEMIRING_LOG, v=phi_q, v_sub=phi_p if sub else None)
+    arc_q, _, _ = label_fold(phi_q, lengths, _C.SEMIRING_LOG)
+    logZ_p, ev, mu_p, hv = deptree_expect(arc_p, lengths, v=dbar, want_mu=wp or wq, want_hv=wp)
+    logZ_q, _, mu_q, _ = deptree_expect(arc_q, lengths, want_mu=wq)
+    ctx.save_for_backward(phi_p, phi_q, arc_p, arc_q, dbar, mu_p, hv, mu_q)
+    ctx.lengths, ctx.sub = lengths, sub
+    return logZ_p, logZ_q, ev
+
+
+def _labeled_pq_backward(ctx, grad_out):
+    "d/d phi_p = -p (hv + mu_p (d - dbar)); d/d phi_q = mu_q q - mu_p p: two mode-1 expands of the same form, so exactly 0 on equal potentials"
+    phi_p, phi_q, arc_p, arc_q, dbar, mu_p, hv, mu_q = ctx.saved_tensors
+    gp = gq = None
+    if ctx.needs_input_grad[0]:
+        gp = _expand_to(phi_p.dtype, phi_p, ctx.lengths, _C.SEMIRING_LOG, arc_p, hv, g2=mu_p, dbar=dbar, v=phi_q,
+                        v_sub=phi_p if ctx.sub else None, scale=-grad_out)
+    if ctx.needs_input_grad[1]:
+        gq = label_expand(phi_q, ctx.lengths, _C.SEMIRING_LOG, arc_q, mu_q, scale=grad_out, mode=1)
+        gq.sub_(label_expand(phi_p, ctx.lengths, _C.SEMIRING_LOG, arc_p, mu_p, scale=grad_out, mode=1))
+        gq = gq.to(phi_q.dtype)
+    return gp, gq, None
+
+
+class _DepTreeLabeledCrossEntropy(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, phi_p, phi_q, lengths):
+        _, logZ_q, ev = _labeled_pq(ctx, phi_p, phi_q, lengths, False)
+        return (logZ_q - ev).to(_out_dtype(phi_p))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        return _labeled_pq_backward(ctx, grad_out)
+
+
+class _DepTreeLabeledKL(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, phi_p, phi_q, lengths):
+        logZ_p, logZ_q, ev = _labeled_pq(ctx, phi_p, phi_q, lengths, True)
+        return (logZ_q - logZ_p - ev).to(_out_dtype(phi_p))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        return _labeled_pq_backward(ctx, grad_out)
+
+
+def _same_labeled_shape(a, b, what):
+    if a.dim() != 4 or tuple(a.shape) != tuple(b.shape):
+        raise ValueError(f"{what} must be labeled like the potentials: {tuple(b.shape)}, got {tuple(a.shape)}")
+
+
+def deptree_labeled_expected_score(phi, lengths, cost):
+    _same_labeled_shape(cost, phi, "cost")
+    return _DepTreeLabeledExpectedScore.apply(phi, lengths, cost)
+
+
+def deptree_labeled_entropy(phi, lengths):
+    return _DepTreeLabeledEntropy.apply(phi, lengths)
+
+
+def deptree_labeled_cross_entropy(phi_p, phi_q, lengths):
+    _same_labeled_shape(phi_q, phi_p, "the other distribution's potentials")
+    return _DepTreeLabeledCrossEntropy.apply(phi_p, phi_q, lengths)
+
+
+def deptree_labeled_kl(phi_p, phi_q, lengths):
+    _same_labeled_shape(phi_q, phi_p, "the other distribution's potentials")
+    return _DepTreeLabeledKL.apply(phi_p, phi_q, lengths)
 
 
 def dmv1o_expect(dec, attach, lengths, v=None, v_sub=None, want_mu=False, want_hv=False):
