@@ -145,6 +145,17 @@ def main():
     stage, mid, out, passes = (float(np.median(rows[:, :, k].max(axis=1))) for k in (5, 6, 7, 4))
     print("## outside the passes (cycles; slowest wavefront, median over the workgroups)")
     print(f"load stage {stage:.0f}  between the passes {mid:.0f}  count write-out {out:.0f}  (inside start -> outside end {passes:.0f})")
+    # the write-out's four sections (short image since round 13; the rows below the first eight; an older build leaves zeros there)
+    split = gdec.view(B, N, 8)[:KBLOCKS, N - 16:N - 8, :4].flip(1).cpu().numpy()   # [block][wave][entry | attach | STOP | GO]
+    if split.any():
+        b_, a_, s_, g_ = (float(np.median(split[:, :, k].max(axis=1))) for k in range(4))
+        print(f"write-out sections: entry {b_:.0f}  attach counts {a_:.0f}  STOP counts {s_:.0f}  GO row sums {g_:.0f}")
+        print("# entry: from the outside pass's last barrier to the write-out's first stamp -- the wavefronts' skew behind that barrier, the")
+        print("#   decode mode's clear + barrier (not in this launch: heads == null), and whatever the compiler moved above the stamp.  The")
+        print("#   stamps order nothing: a section's reads may be issued in the section before it, so only the sum is exact.")
+        print("# load stage: since round 13 stamped at KERNEL ENTRY -- it now includes the kernarg and lengths[b] loads, the range check, the")
+        print("#   chart carve and this diagnostic build's own stamp-table clear + barrier, none of which an earlier build's figure")
+        print("#   (stamped at dmv_run's entry, behind all of them) contains: the new figure is an upper bound of the like-for-like one.")
 
 
 if __name__ == "__main__":

@@ -49,6 +49,8 @@
 #define VLG_MULADD(a, b, c) __builtin_fmaf((a), (b), (c))   // a b + c in ONE rounding, where hipcc's contraction must not be left to chance
 #define VLG_BITS2F(u) __uint_as_float(u)
 #define VLG_ATOMIC_ADD(p, v) atomicAdd((p), (v))
+#define VLG_ASM_UNIFORM(p) "s"(p)   // asm operand: a wave-uniform value, in scalar registers
+#define VLG_OPAQUE(v) asm volatile("" : "+v"(v))   // the compiler forgets what it knows about v: nothing computed from it is shared with code above
 #else
 #include <cmath>
 #include <cstddef>
@@ -66,6 +68,8 @@ static inline float2 make_float2(float a, float b) { float2 r; r.x = a; r.y = b;
 static inline float vlg_bits2f(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
 #define VLG_BITS2F(u) vlg_bits2f(u)
 #define VLG_ATOMIC_ADD(p, v) (*(p) += (v))
+#define VLG_ASM_UNIFORM(p) "r"(p)
+#define VLG_OPAQUE(v) ((void)0)
 #endif
 
 #define VLG_NEGINF (-1e12f)  // semiring zero, semirings.py:16,128 (finite sentinel, never -inf)
@@ -81,6 +85,11 @@ static inline float vlg_bits2f(uint32_t u) { float f; std::memcpy(&f, &u, 4); re
 #define VLG_WSTAMP(x, pass, w, k) (x).wstamp((pass), (w), (k))   // diagnostic build: per-width body-end / barrier-release stamps
 #else                                                            // (VLG_STAMP=2: these alone, tools/time_dp_widths.py)
 #define VLG_WSTAMP(x, pass, w, k) ((void)0)
+#endif
+#if defined(VLG_STAMP) && defined(__HIPCC__)
+#define VLG_OUT_STAMP(st, k) ((st)[k] = __builtin_amdgcn_s_memtime())   // diagnostic build: the count write-out's sections
+#else
+#define VLG_OUT_STAMP(st, k) ((void)0)
 #endif
 // Charts are kept in log2 units so that the hardware's native 2^x / log2 x need no scaling multiplies:
 // potentials are multiplied by log2(e) once at load, logZ by ln(2) once at store; the adjoint weights
@@ -1729,6 +1738,12 @@ VLG_HD void dep_bw_all(const DepCtx& c, int tid, int nt, X& x) {
 // I/O policies of the DMV driver: how one sentence's potentials enter the load stage and where its
 // expected counts go.  `h`, `ch` are positions in the root-augmented sentence (0 = root).
 // ================================================================================================
+// What a lane of the short image's load stage holds for one chart cell (row h, column col) between its requests and its one store:
+// the clamped attach pair of the arc the column stands for (.x HASCHILD, .y NOCHILD) and the four dec entries of head h towards the
+// column's side of the diagonal, as (GO, STOP) of valence 0 and of valence 1 -- natural-log units, clamped, nothing else done to them.
+struct StageCell {
+    float2 att, d0, d1;
+};
 // (a) root-merged potentials -- what `DMV1o([dec, attach], lengths)` takes (distributions.py:245-251).
 template <typename In>
 struct MergedIO {
@@ -1750,6 +1765,25 @@ struct MergedIO {
     VLG_HDM void clear_heads(int tid, int nt) const {
         if (heads) for (int i = tid; i < N; i += nt) heads[i] = 0;
     }
+    // ---- the short image (dmv_stage_request / dmv_counts_out_short) ----
+    // Every element of this sentence's [N][8] / [N][N][2] slices may be read whatever lengths[b] holds: the stage asks for the cells of
+    // all N rows, before the length is known, and discards by select what lies outside the sentence.
+    VLG_HDM int stage_rows(int) const { return N; }
+    VLG_HDM StageCell stage_cell(int h, int ch, int right) const {   // h, ch < N; the diagonal is read like any cell and discarded
+        StageCell s;
+        s.att = ld_attach(h, ch);
+        s.d0 = pot_clamp2(In::ld2(dec, h * 8 + right * 4));
+        s.d1 = pot_clamp2(In::ld2(dec, h * 8 + right * 4 + 2));
+        return s;
+    }
+    // The requests stay where dmv_stage_request makes them: without this the compiler sinks each load behind the branches that lead
+    // to its one use (the length's range check, the cell's bounds test) and the round trips line up again.  An empty statement that
+    // might write through the two pointers: no instruction, no wait.
+    VLG_HDM void stage_pin() const { asm volatile("" : : VLG_ASM_UNIFORM(dec), VLG_ASM_UNIFORM(attach) : "memory"); }
+    VLG_HDM bool wants_heads() const { return heads != nullptr; }
+    VLG_HDM bool wants_attach() const { return gatt != nullptr; }
+    VLG_HDM void st_count(int h, int ch, float2 g) const { *reinterpret_cast<float2*>(gatt + ((size_t)h * N + ch) * 2) = g; }   // wants_attach()
+    VLG_HDM void st_head(int h, int ch) const { heads[ch] = h; }                                                                // wants_heads()
 };
 
 // (b) the scorer's rule tables -- SURVEY.md section 8(f)1.  Folds into the load stage what the reference does
@@ -1801,6 +1835,30 @@ struct RuleIO {
     VLG_HDM void clear_heads(int tid, int nt) const {
         if (heads) for (int i = tid; i < L + 1; i += nt) heads[i] = 0;
     }
+    // ---- the short image (dmv_stage_request / dmv_counts_out_short) ----
+    // The attach read goes through token[], which is checked for the words of the sentence only: the stage asks for the cells of the
+    // sentence's Ne rows, behind the length.
+    VLG_HDM int stage_rows(int Ne) const { return Ne; }
+    VLG_HDM StageCell stage_cell(int h, int ch, int right) const {   // h, ch < Ne
+        StageCell s;
+        s.att = ch != h ? ld_attach(h, ch) : make_float2(VLG_NEGINF, VLG_NEGINF);
+        const int i = h * 8 + right * 4;
+        s.d0 = make_float2(ld_dec(i), ld_dec(i + 1));
+        s.d1 = make_float2(ld_dec(i + 2), ld_dec(i + 3));
+        return s;
+    }
+    VLG_HDM void stage_pin() const {}   // (behind the length already)
+    VLG_HDM bool wants_heads() const { return heads != nullptr; }
+    VLG_HDM bool wants_attach() const { return g_rule != nullptr; }
+    VLG_HDM void st_count(int h, int ch, float2 g) const {   // wants_attach(): the count of st_attach, its head left to st_head
+        if (ch == 0 || h == ch) return;
+        if (h == 0) { if (g.y != 0.f) VLG_ATOMIC_ADD(g_root + token[ch - 1], g.y); return; }
+        if (head_mask && head_mask[h - 1]) return;
+        float* p = g_rule + rule_index(h, ch);
+        if (g.x != 0.f) VLG_ATOMIC_ADD(p, g.x);
+        if (g.y != 0.f) VLG_ATOMIC_ADD(p + 1, g.y);
+    }
+    VLG_HDM void st_head(int h, int ch) const { heads[ch] = h; }   // wants_heads()
 };
 
 // ================================================================================================
@@ -1863,50 +1921,217 @@ VLG_HD void dmv_walk(const DmvCtx& c, float g) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// The short image's load stage and count write-out (round 13).  Both are a handful of accesses per lane; what they cost is the
+// round trips those accesses wait for one after the other, so each is written as "every request, then every use".
+//
+// Load stage.  A lane owns up to kStageCells cells q = tid + k nt of the chart arrays (row h = q / P, column col = q % P) and is
+// their ONLY writer: C[q] and I[q] are stored once, with the semiring zero, the STOP scores (col = h, h + 1: CL(h,h), CR(h,h)) or
+// attach + dec[...,GO] (col < h: arc h -> col; h + 1 < col <= Ne - 1 + 1: arc h -> col - 1) -- no fill, no scatter, no barrier
+// between them.  dmv_stage_request issues what the cell needs from memory (one attach pair, the four dec entries of its side of the
+// diagonal: StageCell) for every cell of `rows` rows, unconditionally -- lanes past the last cell ask for cell 0 -- so the requests
+// are straight-line code that the compiler issues back to back; dmv_stage_write selects.  With MergedIO rows = N, known from the
+// kernel arguments: the kernel entry calls dmv_stage_request BEFORE it reads lengths[b] (vlg_dp_kernels.h: dmv1o_sentence), and
+// the launch pays one memory round trip with the length's scalar load inside it.  The price: a short sentence in a wide tensor reads
+// N P cells' worth of potentials instead of Ne^2 (at most 41 * 43 * (4 + 8) bytes in bf16, mostly the same cache lines).
+// Roundings are the general image's: d = fl(clamp(dec) LOG2E), I = fmaf(clamp(attach), LOG2E, d), STOP cells d itself.
+// ------------------------------------------------------------------------------------------------
+constexpr int kStageCells = 4;
+constexpr int kShortLanesMin = (kShortN * ((kShortN + 1) | 1) + kStageCells - 1) / kStageCells;   // 441: the workgroup has 512
+static_assert(kShortLanesMin <= 2 * VLG_DP_LANES_FW && kShortLanesMin <= 2 * VLG_DP_LANES_BW && kShortN * 8 <= kShortLanesMin,
+              "short image: the chart's N P cells are one pass of kStageCells cells per lane (and so are the N N attach counts, the N 4 "
+              "STOP counts of one lane each and the N 2 GO sums of four lanes each)");
+struct ShortStage {
+    StageCell cell[kStageCells];
+};
+
+template <typename IO>
+VLG_HD ShortStage dmv_stage_request(const IO& io, int P, int rows, int tid, int nt) {
+    ShortStage s;
+    const int cells = rows * P;
+    const float inv_p = 1.0f / (float)P;   // (q + 0.5) * inv_p truncates to q / P exactly for q < 2^16 (margin 0.5 / q >> 2^-23)
+#pragma unroll
+    for (int k = 0; k < kStageCells; ++k) {
+        const int q = tid + k * nt, qq = q < cells ? q : 0;
+        const int h = (int)(((float)qq + 0.5f) * inv_p), col = qq - h * P;
+        const int right = col > h ? 1 : 0, ch = col - right;            // the diagonal's two columns both name (h, h): read, never used
+        s.cell[k] = io.stage_cell(h, ch < rows ? ch : rows - 1, right);   // (columns past the tensor's width: any valid cell)
+    }
+    io.stage_pin();
+    return s;
+}
+
+VLG_HD void dmv_stage_write(const DmvCtx& c, const ShortStage& s, int tid, int nt) {
+    const float2 zz = make_float2(VLG_NEGINF, VLG_NEGINF);
+    const int Ne = c.Ne, P = c.P, cells = Ne * P;
+    const float inv_p = 1.0f / (float)P;
+#pragma unroll
+    for (int k = 0; k < kStageCells; ++k) {
+        const int q = tid + k * nt;
+        if (q >= cells) continue;
+        const int h = (int)(((float)q + 0.5f) * inv_p), col = q - h * P;
+        const StageCell& e = s.cell[k];
+        const float go0 = e.d0.x * VLG_LOG2E, stop0 = e.d0.y * VLG_LOG2E, go1 = e.d1.x * VLG_LOG2E, stop1 = e.d1.y * VLG_LOG2E;
+        const bool arc = col < h || (col > h + 1 && col <= Ne), stop = col == h || col == h + 1;
+        c.I[q] = arc ? make_float2(fmaf(e.att.x, VLG_LOG2E, go0), fmaf(e.att.y, VLG_LOG2E, go1)) : zz;
+        c.C[q] = stop ? make_float2(stop0, stop1) : zz;
+    }
+}
+
+// The count write-out of the other images as a function of its own: for the host test only (see vlg_dp_counts_body.h).
+template <int SR, typename IO, typename X>
+VLG_HD void dmv_counts_out(const DmvCtx& c, const IO& io, int tid, int nt, X& x) {
+    const int Ne = c.Ne, P = c.P;
+    const float2 oo = make_float2(0.f, 0.f);
+#include "vlg_dp_counts_body.h"
+}
+
+// Count write-out.  Every lane's LDS reads are issued before the first is used: at most four attach cells (E E <= 41 * 41, one pass),
+// the two words of a STOP count, the <= ten cells of a GO row sum.  Addresses are selected, not branched on (a cell outside the
+// sentence reads cell 0 and is replaced by zero); the sums keep the general image's order -- k = rr, rr + 4, ..., then the two-step
+// butterfly -- and a term past the row's end leaves the partial sum as it is.
+template <int SR, typename IO, typename X>
+VLG_HD void dmv_counts_out_short(const DmvCtx& c, const IO& io, int tid_in, int nt, X& x, unsigned long long* st) {
+    const int Ne = c.Ne, P = c.P;
+    constexpr int KA = kStageCells;
+    int tid = tid_in;
+    VLG_OPAQUE(tid);   // (or the index arithmetic below is shared with the load stage's and lives in registers through both passes)
+    if (io.wants_heads()) {   // decode mode: heads[] is cleared by other lanes than those that set it.  Otherwise the pass behind us
+        io.clear_heads(tid, nt);   // ended in a barrier and nothing below stores to LDS
+        x.sync();
+    }
+    VLG_OUT_STAMP(st, 0);
+    const int E = io.out_extent(Ne), EE = E * E;
+    const float inv_e = 1.0f / (float)E;
+    int ah[KA], ac[KA];
+    float gx[KA], gy[KA];
+    bool in[KA];
+#pragma unroll
+    for (int k = 0; k < KA; ++k) {
+        const int idx = tid + k * nt;
+        ah[k] = (int)(((float)idx + 0.5f) * inv_e);
+        ac[k] = idx - ah[k] * E;
+        in[k] = idx < EE && ah[k] < Ne && ac[k] < Ne && ac[k] != ah[k];
+        const int cell = ah[k] * P + ac[k] + (ac[k] > ah[k] ? 1 : 0);
+        const float2 g = c.gI[in[k] ? cell : 0];
+        gx[k] = g.x;
+        gy[k] = g.y;
+    }
+#pragma unroll
+    for (int k = 0; k < KA; ++k) {
+        gx[k] = in[k] ? gx[k] : 0.f;
+        gy[k] = in[k] ? gy[k] : 0.f;
+    }
+    if (io.wants_attach()) {
+#pragma unroll
+        for (int k = 0; k < KA; ++k)
+            if (tid + k * nt < EE) io.st_count(ah[k], ac[k], make_float2(gx[k], gy[k]));
+    }
+    if (io.wants_heads()) {
+#pragma unroll
+        for (int k = 0; k < KA; ++k)
+            if (in[k] && gx[k] + gy[k] != 0.f) io.st_head(ah[k], ac[k]);
+    }
+    VLG_OUT_STAMP(st, 1);
+    if (!io.wants_dec()) return;
+    // STOP counts: the adjoint of the width-0 span (one cell each; E * 4 <= 164 lanes)
+    if (tid < E * 4) {
+        const int h = tid >> 2, dir = (tid >> 1) & 1, v = tid & 1;
+        const int hq = h < Ne ? h : 0, q = hq * P + hq + dir;
+        float g;
+        if (SR == VLG_SR_MAX) {
+            g = c.gdecs[hq * 4 + dir * 2 + v];
+        } else {
+            const float gc = c.gCc[q], gi = reinterpret_cast<const float*>(c.gCi + q)[v];
+            g = (v == 1 ? gc : 0.f) + gi;
+        }
+        io.st_dec(h, (dir * 2 + v) * 2 + 1, h < Ne ? g : 0.f);
+    }
+    VLG_OUT_STAMP(st, 2);
+    // GO counts: row sums of the finished gI chart, four lanes per (h, dir) (see the general image below): E * 2 * 4 <= 328 lanes, and
+    // a row has n <= kShortN - 1 cells
+    constexpr int GL = 4, KG = (kShortN - 1 + GL - 1) / GL;
+    const int grp = tid / GL, rr = tid % GL;
+    const int h = grp >> 1, dir = grp & 1;
+    const bool live = grp < E * 2 && h < Ne;
+    const int n = live ? (dir == 0 ? h : Ne - 1 - h) : 0;
+    const float2* row = c.gI + (n > 0 ? h * P + (dir == 0 ? 0 : h + 2) : 0);   // a lane group without terms reads cell 0, inside the chart
+    float tx[KG], ty[KG];
+#pragma unroll
+    for (int j = 0; j < KG; ++j) {
+        const float2 t = row[rr + j * GL < n ? rr + j * GL : 0];
+        tx[j] = t.x;
+        ty[j] = t.y;
+    }
+    VLG_OPAQUE(tx[0]);   // (or the compiler reads the first cell's halves apart, the second one again under its predicate, behind a
+    VLG_OPAQUE(ty[0]);   //  wait of its own.  All reads above are issued by now; this waits for the first of them, as its add would)
+    float sum[2] = {0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < KG; ++j) {
+        const bool on = rr + j * GL < n;
+        sum[0] = on ? sum[0] + tx[j] : sum[0];
+        sum[1] = on ? sum[1] + ty[j] : sum[1];
+    }
+    x.template allreduce_sum<2>(sum, GL);
+    if (grp < E * 2 && rr == 0) {
+        io.st_dec(h, (dir * 2 + 0) * 2, sum[0]);
+        io.st_dec(h, (dir * 2 + 1) * 2, sum[1]);
+    }
+    VLG_OUT_STAMP(st, 3);
+}
+
+// `pre` (short image only): the stage's requests, where the caller has issued them already (dmv1o_sentence: ahead of the length)
 template <int SR, bool BWD, int LONGSPAN = false, typename IO, typename X>
-VLG_HD void dmv_run(const DmvCtx& c, const IO& io, float glogZ, float* logZ, int tid, int nt, X& x) {
+VLG_HD void dmv_run(const DmvCtx& c, const IO& io, float glogZ, float* logZ, int tid, int nt, X& x, const ShortStage* pre = nullptr) {
     const int Ne = c.Ne, P = c.P, len = c.len;
 #if defined(VLG_STAMP) && defined(__HIPCC__)
-    const unsigned long long st_in = __builtin_amdgcn_s_memtime();   // diagnostic build: the load stage begins
+    const unsigned long long st_in = x.t_entry ? x.t_entry : __builtin_amdgcn_s_memtime();   // diagnostic build: the load stage begins
 #endif
     // ---- stage: charts to the semiring zero (dmv.py:34-35), potentials into fast memory -------------------------
-    // The potentials' global loads are issued first and land while the charts are being filled, so the launch pays
-    // one memory latency, not one per dependent step.  Incomplete-span slots are pre-loaded with attach + dec[...,GO]
-    // (dmv.py:36-37); the width-0 complete spans with the STOP scores (dmv.py:39-40).  This folds the reference's
-    // attach_left / attach_right temporaries into the load stage.
+    // Incomplete-span slots are pre-loaded with attach + dec[...,GO] (dmv.py:36-37); the width-0 complete spans with the STOP
+    // scores (dmv.py:39-40).  This folds the reference's attach_left / attach_right temporaries into the load stage.
+    // Short image: the requests were issued by dmv_stage_request (MergedIO kernels: at kernel entry, ahead of the length), each
+    // lane stores its cells of C and I once, and the barrier below is the only one of the stage.  The other images: a lane asks
+    // for up to KC attach cells (each request is waited for where its branch ends -- the gfx950 code has them one after the
+    // other, not in flight together), stages dec through LDS, fills the charts, and scatters behind a barrier of its own.
     const float2 zz = make_float2(VLG_NEGINF, VLG_NEGINF), oo = make_float2(0.f, 0.f);
-    const int NN = Ne * Ne;
-    const float inv_ne = 1.0f / (float)Ne;   // (idx + 0.5) * inv_ne truncates to idx / Ne exactly for idx < 2^16 (margin 0.5 / idx >> 2^-23)
-    constexpr int KC = 4;                    // attach cells per lane in flight
-    for (int base = 0; base < NN; base += KC * nt) {
-        float2 areg[KC];
+    if constexpr (LONGSPAN == kSpansShort) {
+        // every chart cell once, by its one owner (dmv_stage_request): the barrier below is the only one
+        dmv_stage_write(c, pre ? *pre : dmv_stage_request(io, P, io.stage_rows(Ne), tid, nt), tid, nt);
+    } else {
+        const int NN = Ne * Ne;
+        const float inv_ne = 1.0f / (float)Ne;   // (idx + 0.5) * inv_ne truncates to idx / Ne exactly for idx < 2^16 (margin 0.5 / idx >> 2^-23)
+        constexpr int KC = 4;                    // attach cells per lane in flight
+        for (int base = 0; base < NN; base += KC * nt) {
+            float2 areg[KC];
 #pragma unroll
-        for (int k = 0; k < KC; ++k) {
-            const int idx = base + tid + k * nt;
-            const int h = (int)(((float)idx + 0.5f) * inv_ne), ch = idx - h * Ne;
-            areg[k] = (idx < NN && ch != h) ? io.ld_attach(h, ch) : zz;
-        }
-        if (base == 0) {
-            for (int i = tid; i < Ne * 8; i += nt) c.decs[i] = io.ld_dec(i) * VLG_LOG2E;
-            for (int i = tid; i < Ne * P; i += nt) {
-                c.C[i] = zz;
-                c.I[i] = zz;
+            for (int k = 0; k < KC; ++k) {
+                const int idx = base + tid + k * nt;
+                const int h = (int)(((float)idx + 0.5f) * inv_ne), ch = idx - h * Ne;
+                areg[k] = (idx < NN && ch != h) ? io.ld_attach(h, ch) : zz;
             }
-            x.sync();
-        }
+            if (base == 0) {
+                for (int i = tid; i < Ne * 8; i += nt) c.decs[i] = io.ld_dec(i) * VLG_LOG2E;
+                for (int i = tid; i < Ne * P; i += nt) {
+                    c.C[i] = zz;
+                    c.I[i] = zz;
+                }
+                x.sync();
+            }
 #pragma unroll
-        for (int k = 0; k < KC; ++k) {
-            const int idx = base + tid + k * nt;
-            if (idx >= NN) continue;
-            const int h = (int)(((float)idx + 0.5f) * inv_ne), ch = idx - h * Ne;
-            const float* d = c.decs + h * 8;
-            if (ch == h) {
-                c.C[h * P + h] = make_float2(d[1], d[3]);        // CL(h,h).v = dec[h,LEFT ,v,STOP]
-                c.C[h * P + h + 1] = make_float2(d[5], d[7]);    // CR(h,h).v = dec[h,RIGHT,v,STOP]
-            } else if (ch < h) {
-                c.I[h * P + ch] = make_float2(fmaf(areg[k].x, VLG_LOG2E, d[0]), fmaf(areg[k].y, VLG_LOG2E, d[2]));
-            } else {
-                c.I[h * P + ch + 1] = make_float2(fmaf(areg[k].x, VLG_LOG2E, d[4]), fmaf(areg[k].y, VLG_LOG2E, d[6]));
+            for (int k = 0; k < KC; ++k) {
+                const int idx = base + tid + k * nt;
+                if (idx >= NN) continue;
+                const int h = (int)(((float)idx + 0.5f) * inv_ne), ch = idx - h * Ne;
+                const float* d = c.decs + h * 8;
+                if (ch == h) {
+                    c.C[h * P + h] = make_float2(d[1], d[3]);        // CL(h,h).v = dec[h,LEFT ,v,STOP]
+                    c.C[h * P + h + 1] = make_float2(d[5], d[7]);    // CR(h,h).v = dec[h,RIGHT,v,STOP]
+                } else if (ch < h) {
+                    c.I[h * P + ch] = make_float2(fmaf(areg[k].x, VLG_LOG2E, d[0]), fmaf(areg[k].y, VLG_LOG2E, d[2]));
+                } else {
+                    c.I[h * P + ch + 1] = make_float2(fmaf(areg[k].x, VLG_LOG2E, d[4]), fmaf(areg[k].y, VLG_LOG2E, d[6]));
+                }
             }
         }
     }
@@ -1936,7 +2161,8 @@ VLG_HD void dmv_run(const DmvCtx& c, const IO& io, float glogZ, float* logZ, int
     }
     for (int i = tid; i < Ne * P; i += nt) {
         c.gI[i] = oo;
-        if (SR != VLG_SR_MAX) { c.gCc[i] = 0.f; c.gCi[i] = oo; }
+        // (short image: the root's cotangent is stored by the owner of its cell, not behind a barrier of its own)
+        if (SR != VLG_SR_MAX) { c.gCc[i] = (LONGSPAN == kSpansShort && i == len + 1) ? glogZ : 0.f; c.gCi[i] = oo; }
     }
     if (SR == VLG_SR_MAX) for (int i = tid; i < Ne * 4; i += nt) c.gdecs[i] = 0.f;
     x.sync();
@@ -1957,8 +2183,10 @@ VLG_HD void dmv_run(const DmvCtx& c, const IO& io, float glogZ, float* logZ, int
         if (tid == 0) dmv_walk(cb, glogZ);
         x.sync();
     } else {
-    if (tid == 0) c.gCc[len + 1] = glogZ;
-    x.sync();
+    if constexpr (LONGSPAN != kSpansShort) {
+        if (tid == 0) c.gCc[len + 1] = glogZ;
+        x.sync();
+    }
 #if defined(VLG_STAMP) && defined(__HIPCC__)
     {
         const unsigned long long a = __builtin_amdgcn_s_memtime();
@@ -1974,50 +2202,15 @@ VLG_HD void dmv_run(const DmvCtx& c, const IO& io, float glogZ, float* logZ, int
     // expected counts out (coalesced; padded positions get exact zeros like the reference).  Decode mode
     // (heads != null): heads[c] = the h with a non-zero attach count -- what the callers compute on the host
     // with `argmax.sum(-1).nonzero()` + a scatter (ldndmv.py:301-303, joint.py:256-258); 0 for root / padding.
-    io.clear_heads(tid, nt);
-    x.sync();
-    const int E = io.out_extent(Ne);
-    const float inv_e = 1.0f / (float)E;
-    for (int idx = tid; idx < E * E; idx += nt) {
-        const int h = (int)(((float)idx + 0.5f) * inv_e), ch = idx - h * E;
-        float2 g = oo;
-        if (h < Ne && ch < Ne) {
-            if (ch < h) g = c.gI[h * P + ch];
-            else if (ch > h) g = c.gI[h * P + ch + 1];
-        }
-        io.st_attach(h, ch, g);
-    }
-    if (io.wants_dec()) {
-        // STOP counts: the adjoint of the width-0 span (one cell each)
-        for (int idx = tid; idx < E * 4; idx += nt) {
-            const int h = idx >> 2, dir = (idx >> 1) & 1, v = idx & 1;
-            float g = 0.f;
-            if (h < Ne) {
-                const int q = h * P + h + dir;
-                g = SR == VLG_SR_MAX ? c.gdecs[h * 4 + dir * 2 + v] : (v == 1 ? c.gCc[q] : 0.f) + reinterpret_cast<const float*>(c.gCi + q)[v];
-            }
-            io.st_dec(h, (dir * 2 + v) * 2 + 1, g);
-        }
-        // GO counts: dec[h,dir,v,GO] enters every incomplete span headed by h towards dir (dmv.py:36-37), so its count is a sum
-        // over a row of the finished gI chart.  Four lanes per (h, dir) take every fourth cell (both valences at once) and meet in
-        // a two-step butterfly: a fixed summation tree, ~10 dependent LDS reads instead of the 40 of one lane per sum (this loop was
-        // 2.2 us of the 77 us launch as a serial walk).
-        constexpr int GL = 4;
-        for (int base = 0; base < E * 2; base += nt / GL) {
-            const int grp = base + tid / GL, rr = tid % GL;
-            const int h = grp >> 1, dir = grp & 1;
-            float sum[2] = {0.f, 0.f};
-            if (grp < E * 2 && h < Ne) {
-                const float2* row = c.gI + h * P + (dir == 0 ? 0 : h + 2);      // cells (h, ch) for ch < h  |  (h, ch + 1) for ch > h
-                const int n = dir == 0 ? h : Ne - 1 - h;
-                for (int k = rr; k < n; k += GL) { sum[0] += row[k].x; sum[1] += row[k].y; }
-            }
-            x.template allreduce_sum<2>(sum, GL);
-            if (grp < E * 2 && rr == 0) {
-                io.st_dec(h, (dir * 2 + 0) * 2, sum[0]);
-                io.st_dec(h, (dir * 2 + 1) * 2, sum[1]);
-            }
-        }
+#if defined(VLG_STAMP) && defined(__HIPCC__)
+    unsigned long long st_o[4] = {st_end, st_end, st_end, st_end};   // the write-out's sections end: barrier, attach, STOP, GO (short image)
+#else
+    unsigned long long* const st_o = nullptr;
+#endif
+    if constexpr (LONGSPAN == kSpansShort) {
+        dmv_counts_out_short<SR>(c, io, tid, nt, x, st_o);
+    } else {
+#include "vlg_dp_counts_body.h"
     }
 #if defined(VLG_STAMP) && defined(__HIPCC__)
     const unsigned long long st_out = SR == VLG_SR_MAX ? 0 : __builtin_amdgcn_s_memtime() - st_end;   // the count write-out (Log: st_end is taken there)
@@ -2028,9 +2221,13 @@ VLG_HD void dmv_run(const DmvCtx& c, const IO& io, float glogZ, float* logZ, int
         o[4] = (float)(st_end - st_t0); o[5] = (float)st_stage; o[6] = (float)st_mid; o[7] = (float)st_out;
         float* o2 = io.gdec + (size_t)(io.N - 1 - 8 - (tid >> 6)) * 8;
         for (int k = 0; k < 8; ++k) o2[k] = (float)x.acc[k];
+        if (LONGSPAN == kSpansShort && SR != VLG_SR_MAX) {   // (VLG_STAMP=2 leaves acc unused) the write-out's four sections
+            o2[0] = (float)(st_o[0] - st_end); o2[1] = (float)(st_o[1] - st_o[0]); o2[2] = (float)(st_o[2] - st_o[1]); o2[3] = (float)(st_o[3] - st_o[2]);
+        }
     }
 #endif
 }
+
 
 // DepTree: the same walk without valences (single back-pointer per cell).
 VLG_HD void dep_walk(const DepCtx& c, float g) {

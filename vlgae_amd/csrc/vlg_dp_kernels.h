@@ -18,6 +18,7 @@ namespace vlg {
                              //  marginals || Viterbi pair of lang_feat_max_tree went from 101 to 145 us -- so it stays 512.)
 #endif
 constexpr int kThreads = VLG_DP_THREADS;    // lanes per sentence (workgroup size)
+static_assert(kThreads >= kShortLanesMin, "short image: the load stage and the count write-out are one pass of four cells per lane");
 #ifdef VLG_STAMP
 // Diagnostic build (tools/time_dp_widths.py): the DMV1o kernels of the first kStampBlocks sentences copy their per-width stamp table
 // (DevX::wstamp) and each wavefront's HW_ID register to vlg_wstamp_dev; the host reads it with vlg_dp_stamps().
@@ -185,6 +186,7 @@ struct DevX {
         const unsigned t = (unsigned)__builtin_amdgcn_s_memtime();
         if (wst && (threadIdx.x & 63) == 0) wst[((pass * kStampW + w) * 2 + k) * 8 + (threadIdx.x >> 6)] = t;
     }
+    unsigned long long t_entry = 0;   // s_memtime at kernel entry where the kernel took it (dmv1o_sentence), else 0
     unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, last = 0;
     __device__ __forceinline__ void stamp(int k) {   // acc[k & 7] += cycles since the previous stamp
         unsigned long long t;
@@ -283,6 +285,20 @@ __device__ __forceinline__ void dmv1o_sentence(int b, const typename In::T* __re
                                                float* __restrict__ logZ, float* __restrict__ gdec, float* __restrict__ gatt,
                                                long long* __restrict__ heads, char* __restrict__ ws, size_t ws_stride, char* smem) {
     const int tid = threadIdx.x;
+#ifdef VLG_STAMP
+    const unsigned long long t_entry = __builtin_amdgcn_s_memtime();
+#endif
+    // Short image: what the load stage needs from memory is asked for HERE, ahead of lengths[b] -- the cells of all N rows lie inside
+    // this sentence's slices whatever the length holds (vlg_dp_core.h: dmv_stage_request), so the potentials and the length travel
+    // together and the stage pays one memory round trip.  A sentence with an invalid length lets its requests lapse.
+    [[maybe_unused]] ShortStage pre;
+    if constexpr (MODE == kModeShort) {
+        MergedIO<In> in = {};
+        in.dec = dec + (size_t)b * N * 8;
+        in.attach = attach + (size_t)b * N * N * 2;
+        in.N = N;
+        pre = dmv_stage_request(in, chart_pitch(N), N, tid, kThreads);
+    }
     const int len = (int)lengths[b];
     const size_t dec_off = (size_t)b * N * 8, att_off = (size_t)b * N * N * 2;
 
@@ -312,8 +328,12 @@ __device__ __forceinline__ void dmv1o_sentence(int b, const typename In::T* __re
     __syncthreads();
     if ((tid & 63) == 0) wst[kStampWords - 8 + (tid >> 6)] = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // hwreg(HW_REG_HW_ID): SIMD in bits 5:4
     x.wst = wst;
+    x.t_entry = t_entry;
 #endif
-    dmv_run<SR, BWD, spans_of(MODE)>(c, io, (BWD && glogZ) ? glogZ[b] : 1.f, logZ + b, tid, kThreads, x);   // long-sentence placements: chunked long spans
+    if constexpr (MODE == kModeShort)
+        dmv_run<SR, BWD, kSpansShort>(c, io, (BWD && glogZ) ? glogZ[b] : 1.f, logZ + b, tid, kThreads, x, &pre);
+    else
+        dmv_run<SR, BWD, spans_of(MODE)>(c, io, (BWD && glogZ) ? glogZ[b] : 1.f, logZ + b, tid, kThreads, x);   // long-sentence placements: chunked long spans
 #ifdef VLG_STAMP
     __syncthreads();
     if (b < kStampBlocks)
