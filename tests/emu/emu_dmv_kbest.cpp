@@ -12,40 +12,45 @@
 // stand-alone program for the sanitizers, which replays a case file written by the test.
 #include "emu_dp.cpp"
 
+#include "emu_kbest_common.h"
 #include "../../vlgae_amd/csrc/vlg_dmv_kbest.h"
 
 #include <cstdio>
 
 namespace {
 
-struct DmvKbSeqX : HostX {
-    static constexpr int kWave = 1;
-    int lane() const { return 0; }
-};
-
+// plant: -1, or a 16-bit value written over the back-pointer of rank 0 of the root cell before the walks (the walk's give-up rules)
 template <int KC>
-void dmv_kbest_one(const vlg::DmvKbPot& pot, int len, int N, int K, int mode, long long* heads, float* scores, int32_t* count, size_t kb,
-                   int nt, int order) {
+void dmv_kbest_one(const vlg::DmvKbPot& pot, int len, int b, int B, int N, int K, int mode, int plant, long long* heads, float* scores,
+                   int32_t* count, int nt, int order) {
     const vlg::DmvKbestLayout L(N, KC, mode);
-    Arena A(L.lds_bytes), W(L.ws_bytes);
-    for (size_t i = 0; i + 4 <= L.ws_bytes; i += 4) {   // stale workspace contents: quiet NaNs (as floats), 0xffff back-pointers
-        const uint32_t nanbits = 0x7fffffffu;
-        std::memcpy(W.at(i), &nanbits, 4);
-    }
-    auto at = [&](const vlg::Region& r) { return r.lds ? A.at(r.off) : W.at(r.off); };
+    KbArenas m(L.lds_bytes, L.ws_bytes);
     vlg::DmvKbCtx c;
     c.Ne = len + 1; c.len = len; c.P = vlg::chart_pitch(N); c.cells = N * c.P;
-    c.C = (float*)at(L.C); c.T = (float*)at(L.T); c.A = (float*)at(L.A);
-    c.bT = (unsigned short*)at(L.bT); c.bC = (unsigned short*)at(L.bC);
+    c.C = m.at<float>(L.C); c.T = m.at<float>(L.T); c.A = m.at<float>(L.A);
+    c.bT = m.at<unsigned short>(L.bT); c.bC = m.at<unsigned short>(L.bC);
     run_workgroup(nt, order, [&](int tid, HostX& x) { vlg::dmv_kbest_fill<KC>(c, pot, N, tid, nt, x); });
-    if (count) *count = vlg::dmv_kbest_count(c, K);
-    DmvKbSeqX x{};
-    for (int k = 0; k < K; ++k) {
-        int* stack = (int*)at(L.stack) + (k % vlg::kKbestWaves) * vlg::kKbestStack;   // wave k % 8 walks rank k
-        vlg::dmv_kbest_walk<KC>(c, k, N, stack, heads + (size_t)k * kb, scores + (size_t)k * (kb / N), x);
+    if (count) count[b] = vlg::dmv_kbest_count(c, K);
+    if (plant >= 0) c.bC[len + 1 + c.cells] = (unsigned short)plant;   // CR(0,len).NC[0]
+    kbest_each_rank(b, B, N, K, m.at<int>(L.stack), heads, scores,
+                    [&](int k, int* stack, long long* h, float* s, KbSeqX& x) { vlg::dmv_kbest_walk<KC>(c, k, N, stack, h, s, x); });
+    m.check();
+}
+
+int dmv_kbest_batch(const void* dec, const void* attach, const int64_t* lengths, int B, int N, int in_dtype, int K, int mode, const int* plant,
+                    long long* heads, float* scores, int32_t* count, int nt, int order) {
+    if (K < 1 || K > vlg::kKbestMaxK || N < 2 || N > 255) return -1;
+    const vlg::KbestPlan p = vlg::dmv_kbest_plan(N, K, vlg::kLdsBudget);
+    if (mode < 0) mode = p.mode;
+    for (int b = 0; b < B; ++b) {
+        const int len = (int)lengths[b];
+        if (kbest_no_sentence(len, b, B, N, K, heads, scores, count)) continue;
+        const vlg::DmvKbPot pot{dec, attach, (size_t)b * N * 8, (size_t)b * N * N * 2, in_dtype};
+        kbest_image_switch(p.KC, [&](auto kc) {
+            dmv_kbest_one<decltype(kc)::value>(pot, len, b, B, N, K, mode, plant ? plant[b] : -1, heads, scores, count, nt, order);
+        });
     }
-    A.check();
-    W.check();
+    return 0;
 }
 
 }  // namespace
@@ -53,40 +58,16 @@ void dmv_kbest_one(const vlg::DmvKbPot& pot, int len, int N, int K, int mode, lo
 // heads [K,B,N], scores [K,B], count [B] (optional); mode: the DmvKbestLayout placement to emulate (any N), or -1 for the plan's own
 extern "C" int emu_dmv1o_kbest(const void* dec, const void* attach, const int64_t* lengths, int B, int N, int in_dtype, int K, int mode,
                                long long* heads, float* scores, int32_t* count, int nt, int order) {
-    if (K < 1 || K > vlg::kKbestMaxK || N < 2 || N > 255) return -1;
-    const vlg::KbestPlan p = vlg::dmv_kbest_plan(N, K, vlg::kLdsBudget);
-    if (mode < 0) mode = p.mode;
-    for (int b = 0; b < B; ++b) {
-        const int len = (int)lengths[b];
-        long long* h = heads + (size_t)b * N;
-        float* s = scores + b;
-        if (len < 1 || len > N - 1) {
-            for (int k = 0; k < K; ++k) {
-                for (int i = 0; i < N; ++i) h[(size_t)k * B * N + i] = 0;
-                s[(size_t)k * B] = std::nanf("");
-            }
-            if (count) count[b] = 0;
-            continue;
-        }
-        const vlg::DmvKbPot pot{dec, attach, (size_t)b * N * 8, (size_t)b * N * N * 2, in_dtype};
-        int32_t* cnt = count ? count + b : nullptr;
-        const size_t kb = (size_t)B * N;
-        switch (p.KC) {
-            case 1: dmv_kbest_one<1>(pot, len, N, K, mode, h, s, cnt, kb, nt, order); break;
-            case 2: dmv_kbest_one<2>(pot, len, N, K, mode, h, s, cnt, kb, nt, order); break;
-            case 4: dmv_kbest_one<4>(pot, len, N, K, mode, h, s, cnt, kb, nt, order); break;
-            case 8: dmv_kbest_one<8>(pot, len, N, K, mode, h, s, cnt, kb, nt, order); break;
-            default: dmv_kbest_one<16>(pot, len, N, K, mode, h, s, cnt, kb, nt, order); break;
-        }
-    }
-    return 0;
+    return dmv_kbest_batch(dec, attach, lengths, B, N, in_dtype, K, mode, nullptr, heads, scores, count, nt, order);
 }
 
-// the layout as the kernel carves it, for the tests' restatement: out = {KC, mode, lds_bytes, ws_stride} of the plan
-extern "C" void emu_dmv_kbest_plan(int N, int K, long long* out) {
-    const vlg::KbestPlan p = vlg::dmv_kbest_plan(N, K, vlg::kLdsBudget);
-    out[0] = p.KC; out[1] = p.mode; out[2] = (long long)p.lds_bytes; out[3] = (long long)p.ws_stride;
+// the same with plant [B]: per sentence -1, or the value that replaces the back-pointer of rank 0 of its root cell behind the fill
+extern "C" int emu_dmv1o_kbest_planted(const void* dec, const void* attach, const int64_t* lengths, int B, int N, int in_dtype, int K,
+                                       int mode, const int* plant, long long* heads, float* scores, int32_t* count, int nt, int order) {
+    return dmv_kbest_batch(dec, attach, lengths, B, N, in_dtype, K, mode, plant, heads, scores, count, nt, order);
 }
+
+extern "C" void emu_dmv_kbest_plan(int N, int K, long long* out) { kbest_plan_export<vlg::DmvKbestLayout>(N, K, out); }
 
 // vlg_dmv1o_tree_counts: the kernel's frame around dmv_tree_counts_lane, one lane after the other
 extern "C" int emu_dmv1o_tree_counts(const long long* heads, const int64_t* lengths, const int32_t* count, const float* weight, int T, int B,

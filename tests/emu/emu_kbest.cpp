@@ -10,40 +10,44 @@
 // stand-alone program for the sanitizers, which replays a case file written by the test.
 #include "emu_dp.cpp"
 
-#include "../../vlgae_amd/csrc/vlg_dp_kbest.h"
+#include "emu_kbest_common.h"
 
 #include <cstdio>
 
 namespace {
 
-struct KbSeqX : HostX {
-    static constexpr int kWave = 1;
-    int lane() const { return 0; }
-};
-
+// plant: -1, or a 16-bit value written over the back-pointer of rank 0 of the root cell before the walks (the walk's give-up rules)
 template <int KC>
-void kbest_one(const vlg::KbArc& arc, int len, int N, int K, int mode, long long* heads, float* scores, int32_t* count, size_t kb,
-               int nt, int order) {
+void kbest_one(const vlg::KbArc& arc, int len, int b, int B, int N, int K, int mode, int plant, long long* heads, float* scores,
+               int32_t* count, int nt, int order) {
     const vlg::KbestLayout L(N, KC, mode);
-    Arena A(L.lds_bytes), W(L.ws_bytes);
-    for (size_t i = 0; i + 4 <= L.ws_bytes; i += 4) {   // stale workspace contents: quiet NaNs (as floats), 0xffff back-pointers
-        const uint32_t nanbits = 0x7fffffffu;
-        std::memcpy(W.at(i), &nanbits, 4);
-    }
-    auto at = [&](const vlg::Region& r) { return r.lds ? A.at(r.off) : W.at(r.off); };
+    KbArenas m(L.lds_bytes, L.ws_bytes);
     vlg::KbCtx c;
     c.Ne = len + 1; c.len = len; c.P = vlg::chart_pitch(N); c.cells = N * c.P;
-    c.C = (float*)at(L.C); c.I = (float*)at(L.I);
-    c.bT = (unsigned short*)at(L.bT); c.bC = (unsigned short*)at(L.bC);
+    c.C = m.at<float>(L.C); c.I = m.at<float>(L.I);
+    c.bT = m.at<unsigned short>(L.bT); c.bC = m.at<unsigned short>(L.bC);
     run_workgroup(nt, order, [&](int tid, HostX& x) { vlg::kbest_fill<KC>(c, arc, N, tid, nt, x); });
-    if (count) *count = vlg::kbest_count(c, K);
-    KbSeqX x{};
-    for (int k = 0; k < K; ++k) {
-        int* stack = (int*)at(L.stack) + (k % vlg::kKbestWaves) * vlg::kKbestStack;   // wave k % 8 walks rank k
-        vlg::kbest_walk<KC>(c, k, N, stack, heads + (size_t)k * kb, scores + (size_t)k * (kb / N), x);
+    if (count) count[b] = vlg::kbest_count(c, K);
+    if (plant >= 0) c.bC[len + 1] = (unsigned short)plant;   // CR(0,len)[0]
+    kbest_each_rank(b, B, N, K, m.at<int>(L.stack), heads, scores,
+                    [&](int k, int* stack, long long* h, float* s, KbSeqX& x) { vlg::kbest_walk<KC>(c, k, N, stack, h, s, x); });
+    m.check();
+}
+
+int kbest_batch(const void* arc, const int64_t* lengths, int B, int N, int in_dtype, int K, int mode, const int* plant, long long* heads,
+                float* scores, int32_t* count, int nt, int order) {
+    if (K < 1 || K > vlg::kKbestMaxK || N < 2 || N > 255) return -1;
+    const vlg::KbestPlan p = vlg::kbest_plan(N, K, vlg::kLdsBudget);
+    if (mode < 0) mode = p.mode;
+    for (int b = 0; b < B; ++b) {
+        const int len = lengths ? (int)lengths[b] : N - 1;
+        if (kbest_no_sentence(len, b, B, N, K, heads, scores, count)) continue;
+        const vlg::KbArc a{arc, (size_t)b * N * N, in_dtype};
+        kbest_image_switch(p.KC, [&](auto kc) {
+            kbest_one<decltype(kc)::value>(a, len, b, B, N, K, mode, plant ? plant[b] : -1, heads, scores, count, nt, order);
+        });
     }
-    A.check();
-    W.check();
+    return 0;
 }
 
 }  // namespace
@@ -51,40 +55,16 @@ void kbest_one(const vlg::KbArc& arc, int len, int N, int K, int mode, long long
 // heads [K,B,N], scores [K,B], count [B] (optional); mode: the KbestLayout placement to emulate (any N), or -1 for the plan's own
 extern "C" int emu_deptree_kbest(const void* arc, const int64_t* lengths, int B, int N, int in_dtype, int K, int mode, long long* heads,
                                  float* scores, int32_t* count, int nt, int order) {
-    if (K < 1 || K > vlg::kKbestMaxK || N < 2 || N > 255) return -1;
-    const vlg::KbestPlan p = vlg::kbest_plan(N, K, vlg::kLdsBudget);
-    if (mode < 0) mode = p.mode;
-    for (int b = 0; b < B; ++b) {
-        const int len = lengths ? (int)lengths[b] : N - 1;
-        long long* h = heads + (size_t)b * N;
-        float* s = scores + b;
-        if (len < 1 || len > N - 1) {
-            for (int k = 0; k < K; ++k) {
-                for (int i = 0; i < N; ++i) h[(size_t)k * B * N + i] = 0;
-                s[(size_t)k * B] = std::nanf("");
-            }
-            if (count) count[b] = 0;
-            continue;
-        }
-        const vlg::KbArc a{arc, (size_t)b * N * N, in_dtype};
-        int32_t* cnt = count ? count + b : nullptr;
-        const size_t kb = (size_t)B * N;
-        switch (p.KC) {
-            case 1: kbest_one<1>(a, len, N, K, mode, h, s, cnt, kb, nt, order); break;
-            case 2: kbest_one<2>(a, len, N, K, mode, h, s, cnt, kb, nt, order); break;
-            case 4: kbest_one<4>(a, len, N, K, mode, h, s, cnt, kb, nt, order); break;
-            case 8: kbest_one<8>(a, len, N, K, mode, h, s, cnt, kb, nt, order); break;
-            default: kbest_one<16>(a, len, N, K, mode, h, s, cnt, kb, nt, order); break;
-        }
-    }
-    return 0;
+    return kbest_batch(arc, lengths, B, N, in_dtype, K, mode, nullptr, heads, scores, count, nt, order);
 }
 
-// the layout as the kernel carves it, for the tests' restatement: out = {KC, mode, lds_bytes, ws_stride} of the plan
-extern "C" void emu_kbest_plan(int N, int K, long long* out) {
-    const vlg::KbestPlan p = vlg::kbest_plan(N, K, vlg::kLdsBudget);
-    out[0] = p.KC; out[1] = p.mode; out[2] = (long long)p.lds_bytes; out[3] = (long long)p.ws_stride;
+// the same with plant [B]: per sentence -1, or the value that replaces the back-pointer of rank 0 of its root cell behind the fill
+extern "C" int emu_deptree_kbest_planted(const void* arc, const int64_t* lengths, int B, int N, int in_dtype, int K, int mode,
+                                         const int* plant, long long* heads, float* scores, int32_t* count, int nt, int order) {
+    return kbest_batch(arc, lengths, B, N, in_dtype, K, mode, plant, heads, scores, count, nt, order);
 }
+
+extern "C" void emu_kbest_plan(int N, int K, long long* out) { kbest_plan_export<vlg::KbestLayout>(N, K, out); }
 
 #ifdef EMU_KBEST_MAIN
 // emu_kbest CASEFILE: int32 B, N, K, mode; int64 lengths[B]; float arc[B N N]; float expect_scores[K B]; int64 expect_heads[K B N].

@@ -22,8 +22,8 @@ from dmv_sample_restatement import tree_score
 HERE = os.path.join(ROOT, "tests", "emu")
 BUILD = os.path.join(HERE, "_build")
 SRC = os.path.join(HERE, "emu_dmv_kbest.cpp")
-DEPS = [SRC, os.path.join(HERE, "emu_dp.cpp")] + [os.path.join(ROOT, "vlgae_amd", "csrc", f)
-                                                  for f in ("vlg_dp_core.h", "vlg_dp_kbest.h", "vlg_dmv_kbest.h")]
+DEPS = [SRC, os.path.join(HERE, "emu_dp.cpp"), os.path.join(HERE, "emu_kbest_common.h")] + [
+    os.path.join(ROOT, "vlgae_amd", "csrc", f) for f in ("vlg_dp_core.h", "vlg_dp_kbest.h", "vlg_dmv_kbest.h")]
 NS = (2, 3, 6, 12, 41, 66)
 KS = (1, 2, 3, 4, 5, 8, 9, 16)
 LDS = 160 * 1024

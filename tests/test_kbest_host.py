@@ -21,7 +21,8 @@ from conftest import GOLDEN, ROOT, load
 HERE = os.path.join(ROOT, "tests", "emu")
 BUILD = os.path.join(HERE, "_build")
 SRC = os.path.join(HERE, "emu_kbest.cpp")
-DEPS = [SRC, os.path.join(HERE, "emu_dp.cpp")] + [os.path.join(ROOT, "vlgae_amd", "csrc", f) for f in ("vlg_dp_core.h", "vlg_dp_kbest.h")]
+DEPS = [SRC, os.path.join(HERE, "emu_dp.cpp"), os.path.join(HERE, "emu_kbest_common.h")] + [
+    os.path.join(ROOT, "vlgae_amd", "csrc", f) for f in ("vlg_dp_core.h", "vlg_dp_kbest.h")]
 NS = (2, 3, 6, 12, 41, 66)
 KS = (1, 2, 3, 4, 5, 8, 9, 16)
 FIXTURES = (("kbest_B3_N6_K4_s0", 4), ("kbest_B4_N12_K8_s1", 8), ("kbest_B2_N41_K16_s2", 16))

@@ -1,7 +1,8 @@
 // vlg_dmv_kbest.h -- the K best projective single-root trees of the valence DMV (DMV1o.kbest_heads / kbest_scores), and the adjoint of
 // their scores (the derivation counts of given trees).
 //
-// The valence-aware sibling of vlg_dp_kbest.h, whose candidate lists, total order, pruning bound and placement scheme it reuses: per-lane
+// The valence-aware sibling of vlg_dp_kbest.h, whose candidate lists, total order, pruning bound, placement scheme, count
+// and walk frame (entry packing, start, back-pointer checks, finish) it reuses: per-lane
 // / per-group / per-wave bodies written against a policy X, shared by the gfx950 kernels (vlg_dmv_kbest.hip) and the host emulator of
 // the CPU test-suite (tests/emu/emu_dmv_kbest.cpp).  Nothing here is a CPU fallback.
 //
@@ -49,14 +50,7 @@ struct DmvKbestLayout {
     }
 };
 
-// the one place that chooses: the first placement that fits the LDS (the launcher and the size query both ask here)
-VLG_HOSTDEV KbestPlan dmv_kbest_plan(int N, int K, size_t lds_budget) {
-    const int KC = kbest_image(K);
-    int mode = 0;
-    while (mode < 2 && DmvKbestLayout(N, KC, mode).lds_bytes > lds_budget) ++mode;
-    const DmvKbestLayout L(N, KC, mode);
-    return KbestPlan{KC, mode, L.lds_bytes, L.ws_bytes};
-}
+VLG_HOSTDEV KbestPlan dmv_kbest_plan(int N, int K, size_t lds_budget) { return kbest_plan_of<DmvKbestLayout>(N, K, lds_budget); }
 
 struct DmvKbCtx {
     int Ne, len, P, cells;   // cells = N * P: the distance between two planes
@@ -199,25 +193,15 @@ VLG_HD void dmv_kbest_fill(const DmvKbCtx& c, const DmvKbPot& pot, int N, int ti
     }
 }
 
-// walk entries: kbest_entry's kinds (0 = IL(hi -> lo), 1 = CL(hi -> lo), 2 = CR(lo -> hi), 3 = IR(lo -> hi)) and rank, plus the valence
-VLG_HD int dmv_kbest_entry(int kind, int lo, int hi, int rank, int v) { return kbest_entry(kind, lo, hi, rank) | (v << 22); }
-
-// Rank k of one sentence, by one wavefront: kbest_walk with valences.  Width-0 leaves are not pushed.  Same give-up rules: after 4 N
-// visits, on a back-pointer that does not fit its cell or on a full stack -- heads 0, score NaN.
+// Rank k of one sentence, by one wavefront: kbest_walk with valences, around the same start, checks and finish.
 template <int KC, typename X>
 VLG_HD void dmv_kbest_walk(const DmvKbCtx& c, int k, int N, int* stack, long long* heads, float* score, X& x) {
     const int len = c.len, P = c.P, cells = c.cells, lane = x.lane();
     const float s = c.C[len + 1 + (2 * k + 1) * cells];   // CR(0,len).NC[k]
-    const bool exists = s > 0.5f * VLG_NEGINF;
-    for (int i = lane; i < N; i += X::kWave)
-        if (!exists || i == 0 || i > len) heads[i] = 0;   // every word 1 ... len gets its head from the walk: one writer per element
-    if (!exists) {
-        if (lane == 0) *score = VLG_NEGINF;
-        return;
-    }
+    if (!kbest_walk_begin(s, len, N, heads, score, x)) return;
     int top = 0, visits = 0;
     bool ok = true;
-    int e = dmv_kbest_entry(2, 0, len, k, 1);
+    int e = kbest_entry(2, 0, len, k, 1);
     for (;;) {
         const int kind = e & 3, lo = (e >> 2) & 255, hi = (e >> 10) & 255, rk = (e >> 18) & 15, v = (e >> 22) & 1;
         if (++visits > 4 * N) { ok = false; break; }
@@ -231,15 +215,15 @@ VLG_HD void dmv_kbest_walk(const DmvKbCtx& c, int k, int N, int* stack, long lon
             bp = c.bC[(kind == 1 ? hi * P + lo : D + w + 1) + (2 * rk + v) * cells];
         }
         bp = x.uniform(bp);
+        if (!kbest_bp_fits<KC>(bp, w)) { ok = false; break; }
         const int r = bp >> 8, p = (bp >> 4) & 15, q = bp & 15;
-        if (r >= w || p >= KC || q >= KC) { ok = false; break; }
         int ea, eb;   // the two children, their valences by the parent's kind (dmv_sample_walk)
-        if (kind == 0) { ea = dmv_kbest_entry(2, lo, lo + r, p, 1); eb = dmv_kbest_entry(1, lo + r + 1, hi, q, 0); }
-        else if (kind == 3) { ea = dmv_kbest_entry(2, lo, lo + r, p, 0); eb = dmv_kbest_entry(1, lo + r + 1, hi, q, 1); }
-        else if (kind == 1) { ea = dmv_kbest_entry(1, lo, lo + r, p, 1); eb = dmv_kbest_entry(0, lo + r, hi, q, v); }
-        else { ea = dmv_kbest_entry(3, lo, lo + 1 + r, p, v); eb = dmv_kbest_entry(2, lo + 1 + r, hi, q, 1); }
-        int wa = ((ea >> 10) & 255) - ((ea >> 2) & 255), wb = ((eb >> 10) & 255) - ((eb >> 2) & 255);
-        if ((wa == 0 && ((ea >> 18) & 15) != 0) || (wb == 0 && ((eb >> 18) & 15) != 0)) { ok = false; break; }   // a trivial cell has rank 0 only
+        if (kind == 0) { ea = kbest_entry(2, lo, lo + r, p, 1); eb = kbest_entry(1, lo + r + 1, hi, q, 0); }
+        else if (kind == 3) { ea = kbest_entry(2, lo, lo + r, p, 0); eb = kbest_entry(1, lo + r + 1, hi, q, 1); }
+        else if (kind == 1) { ea = kbest_entry(1, lo, lo + r, p, 1); eb = kbest_entry(0, lo + r, hi, q, v); }
+        else { ea = kbest_entry(3, lo, lo + 1 + r, p, v); eb = kbest_entry(2, lo + 1 + r, hi, q, 1); }
+        int wa = kbest_entry_width(ea), wb = kbest_entry_width(eb);
+        if (!kbest_child_fits(ea, wa) || !kbest_child_fits(eb, wb)) { ok = false; break; }
         if (wa > wb) { const int te = ea; ea = eb; eb = te; const int tw = wa; wa = wb; wb = tw; }   // ea: the narrower one
         if (wa > 0) {
             if (top >= kKbestStack) { ok = false; break; }
@@ -252,19 +236,11 @@ VLG_HD void dmv_kbest_walk(const DmvKbCtx& c, int k, int N, int* stack, long lon
             e = x.uniform(stack[--top]);
         }
     }
-    if (lane == 0) {
-        if (!ok)
-            for (int i = 0; i < N; ++i) heads[i] = 0;   // one lane, in program order behind its own stores above
-        *score = ok ? s : VLG_BITS2F(0x7fc00000u);
-    }
+    kbest_walk_finish(ok, s, N, heads, score, lane);
 }
 
 // how many of the first K ranks exist
-VLG_HD int dmv_kbest_count(const DmvKbCtx& c, int K) {
-    int n = 0;
-    for (int k = 0; k < K; ++k) n += c.C[c.len + 1 + (2 * k + 1) * c.cells] > 0.5f * VLG_NEGINF ? 1 : 0;
-    return n;
-}
+VLG_HD int dmv_kbest_count(const DmvKbCtx& c, int K) { return kbest_count_at(c.C, c.len + 1 + c.cells, 2 * c.cells, K); }   // CR(0,len).NC[k]
 
 // ---- the adjoint of the scores: derivation counts of given trees ------------------------------------------------------------------
 // Lane i of one tree of one sentence.  hs [N]: the tree's heads, -1 where the entry is outside 0 ... len or names the word itself

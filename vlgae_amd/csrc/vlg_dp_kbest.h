@@ -2,6 +2,11 @@
 //
 // Like vlg_dp_sample.h: per-lane / per-group / per-wave bodies written against a policy X, shared by the gfx950 kernel
 // (vlg_kbest.hip) and the host emulator of the CPU test-suite (tests/emu/emu_kbest.cpp).  Nothing here is a CPU fallback.
+// The valence DMV's kernel (vlg_dmv_kbest.h) takes from here what does not depend on the model: the plan, the candidate lists, the
+// walk's entry packing, start, back-pointer checks and finish, and the count.  Each model keeps its span body
+// with the KC extraction rounds at its end, its span-width loop, and the loop of its walk, which reads a cell's back-pointer, names
+// its children and steps: written once over both they moved SGPR counts and spills of the images or cost the DepTree kernel time
+// (profiles/kbest_frame_neutrality.md).
 //
 // Chart geometry is DepCtx's (vlg_dp_core.h), with KC values per cell instead of one, sorted in descending order; KC is the
 // compile-time image that serves the caller's K (kbest_image).  Rank k of cell x lives at chart[k * cells + x] ("rank planes"): the
@@ -60,14 +65,18 @@ struct KbestLayout {
 
 struct KbestPlan { int KC, mode; size_t lds_bytes, ws_stride; };   // code image; placement; dynamic LDS; workspace bytes per sentence
 
-// the one place that chooses: the first placement that fits the LDS (the launcher and the size query both ask here)
-VLG_HOSTDEV KbestPlan kbest_plan(int N, int K, size_t lds_budget) {
+// the one place that chooses: the first placement of a Layout (KbestLayout, DmvKbestLayout) that fits the LDS (the launchers, the
+// size queries and the emulators all ask here)
+template <typename Layout>
+VLG_HOSTDEV KbestPlan kbest_plan_of(int N, int K, size_t lds_budget) {
     const int KC = kbest_image(K);
     int mode = 0;
-    while (mode < 2 && KbestLayout(N, KC, mode).lds_bytes > lds_budget) ++mode;
-    const KbestLayout L(N, KC, mode);
+    while (mode < 2 && Layout(N, KC, mode).lds_bytes > lds_budget) ++mode;
+    const Layout L(N, KC, mode);
     return KbestPlan{KC, mode, L.lds_bytes, L.ws_bytes};
 }
+
+VLG_HOSTDEV KbestPlan kbest_plan(int N, int K, size_t lds_budget) { return kbest_plan_of<KbestLayout>(N, K, lds_budget); }
 
 struct KbCtx {
     int Ne, len, P, cells;   // cells = N * P: the distance between two rank planes
@@ -227,25 +236,53 @@ VLG_HD void kbest_fill(const KbCtx& c, const KbArc& arc, int N, int tid, int nt,
     }
 }
 
-// walk entries: 0 = IL(hi -> lo), 1 = CL(hi -> lo), 2 = CR(lo -> hi), 3 = IR(lo -> hi), with the rank of the cell's derivation
-VLG_HD int kbest_entry(int kind, int lo, int hi, int rank) { return kind | (lo << 2) | (hi << 10) | (rank << 18); }
+// ---- the walk: rank k of one sentence, by one wavefront (its control flow is wave-uniform; lane 0 writes the heads).  heads: the N
+// int64 of this (rank, sentence); score: its cell; stack: kKbestStack ints of this wave.  Behind the last barrier of the fill the
+// charts are read-only.  A rank that does not exist gets heads 0 and VLG_NEGINF and is not walked.  The walk visits every non-trivial
+// cell of the tree once (at most 3 len + 1); width-0 leaves are not pushed.  After 4 N visits, on a back-pointer that does not fit
+// its cell or on a full stack it gives up -- heads 0, score NaN -- so that no chart contents can make it spin or read outside the
+// charts.  A model's walk (kbest_walk here, dmv_kbest_walk) reads the back-pointer of a cell, names its two children, descends into
+// the narrower one and leaves the wider one pending; the entry packing, the start, the checks of a back-pointer and the finish are the
+// ones below.  (The descend / push / pop step stands in each walk: as the samplers' sample_order / sample_step it cost the DepTree
+// walk 4 us of 105 at B = 256, N = 41, K = 1, profiles/kbest_frame_neutrality.md.)
 
-// Rank k of one sentence, by one wavefront (its control flow is wave-uniform; lane 0 writes the heads).  heads: the N int64 of this
-// (rank, sentence); score: its cell; stack: kKbestStack ints of this wave.  Behind the last barrier of kbest_fill the charts are
-// read-only.  A rank that does not exist gets heads 0 and VLG_NEGINF and is not walked.  The walk visits every non-trivial cell of
-// the tree once (at most 3 len + 1); after 4 N visits, on a back-pointer that does not fit its cell or on a full stack it gives up
-// -- heads 0, score NaN -- so that no chart contents can make it spin or read outside the charts.
+// walk entries: 0 = IL(hi -> lo), 1 = CL(hi -> lo), 2 = CR(lo -> hi), 3 = IR(lo -> hi), with the rank of the cell's derivation and,
+// where the model has one, its valence
+VLG_HD int kbest_entry(int kind, int lo, int hi, int rank, int v = 0) { return kind | (lo << 2) | (hi << 10) | (rank << 18) | (v << 22); }
+VLG_HD int kbest_entry_width(int e) { return ((e >> 10) & 255) - ((e >> 2) & 255); }
+
+// s: the value of rank k of the root cell.  False where the rank does not exist: heads 0, score VLG_NEGINF.  Else the heads of the
+// positions that are no word are 0 -- every word 1 ... len gets its head from the walk: one writer per element.
+template <typename X>
+VLG_HD bool kbest_walk_begin(float s, int len, int N, long long* heads, float* score, X& x) {
+    const bool exists = s > 0.5f * VLG_NEGINF;
+    for (int i = x.lane(); i < N; i += X::kWave)
+        if (!exists || i == 0 || i > len) heads[i] = 0;
+    if (!exists && x.lane() == 0) *score = VLG_NEGINF;
+    return exists;
+}
+
+// the back-pointer r << 8 | p << 4 | q fits a cell of width w in the image KC
+template <int KC>
+VLG_HD bool kbest_bp_fits(int bp, int w) { return (bp >> 8) < w && ((bp >> 4) & 15) < KC && (bp & 15) < KC; }
+
+// a child entry of width w names a rank its cell can have: a trivial cell has rank 0 only
+VLG_HD bool kbest_child_fits(int e, int w) { return w != 0 || ((e >> 18) & 15) == 0; }
+
+// the end of a walk: the score s, or -- it gave up -- heads 0 and score NaN
+VLG_HD void kbest_walk_finish(bool ok, float s, int N, long long* heads, float* score, int lane) {
+    if (lane == 0) {
+        if (!ok)
+            for (int i = 0; i < N; ++i) heads[i] = 0;   // one lane, in program order behind its own stores above
+        *score = ok ? s : VLG_BITS2F(0x7fc00000u);
+    }
+}
+
 template <int KC, typename X>
 VLG_HD void kbest_walk(const KbCtx& c, int k, int N, int* stack, long long* heads, float* score, X& x) {
     const int len = c.len, P = c.P, cells = c.cells, lane = x.lane();
     const float s = c.C[len + 1 + k * cells];   // CR(0,len)[k]
-    const bool exists = s > 0.5f * VLG_NEGINF;
-    for (int i = lane; i < N; i += X::kWave)
-        if (!exists || i == 0 || i > len) heads[i] = 0;   // every word 1 ... len gets its head from the walk: one writer per element
-    if (!exists) {
-        if (lane == 0) *score = VLG_NEGINF;
-        return;
-    }
+    if (!kbest_walk_begin(s, len, N, heads, score, x)) return;
     int top = 0, visits = 0;
     bool ok = true;
     int e = kbest_entry(2, 0, len, k);
@@ -264,14 +301,14 @@ VLG_HD void kbest_walk(const KbCtx& c, int k, int N, int* stack, long long* head
             bp = c.bC[D + w + 1 + ko];
         }
         bp = x.uniform(bp);
+        if (!kbest_bp_fits<KC>(bp, w)) { ok = false; break; }
         const int r = bp >> 8, p = (bp >> 4) & 15, q = bp & 15;
-        if (r >= w || p >= KC || q >= KC) { ok = false; break; }
         int ea, eb;   // the two children
         if (inc) { ea = kbest_entry(2, lo, lo + r, p); eb = kbest_entry(1, lo + r + 1, hi, q); }
         else if (kind == 1) { ea = kbest_entry(1, lo, lo + r, p); eb = kbest_entry(0, lo + r, hi, q); }
         else { ea = kbest_entry(3, lo, lo + 1 + r, p); eb = kbest_entry(2, lo + 1 + r, hi, q); }
-        int wa = ((ea >> 10) & 255) - ((ea >> 2) & 255), wb = ((eb >> 10) & 255) - ((eb >> 2) & 255);
-        if ((wa == 0 && (ea >> 18) != 0) || (wb == 0 && (eb >> 18) != 0)) { ok = false; break; }   // a trivial cell has rank 0 only
+        int wa = kbest_entry_width(ea), wb = kbest_entry_width(eb);
+        if (!kbest_child_fits(ea, wa) || !kbest_child_fits(eb, wb)) { ok = false; break; }
         if (wa > wb) { const int te = ea; ea = eb; eb = te; const int tw = wa; wa = wb; wb = tw; }   // ea: the narrower one
         if (wa > 0) {
             if (top >= kKbestStack) { ok = false; break; }
@@ -284,18 +321,15 @@ VLG_HD void kbest_walk(const KbCtx& c, int k, int N, int* stack, long long* head
             e = x.uniform(stack[--top]);
         }
     }
-    if (lane == 0) {
-        if (!ok)
-            for (int i = 0; i < N; ++i) heads[i] = 0;   // one lane, in program order behind its own stores above
-        *score = ok ? s : VLG_BITS2F(0x7fc00000u);
-    }
+    kbest_walk_finish(ok, s, N, heads, score, lane);
 }
 
-// how many of the first K ranks exist
-VLG_HD int kbest_count(const KbCtx& c, int K) {
+// how many of the first K ranks exist; rank k of the root cell at C[root + k stride]
+VLG_HD int kbest_count_at(const float* C, int root, int stride, int K) {
     int n = 0;
-    for (int k = 0; k < K; ++k) n += c.C[c.len + 1 + k * c.cells] > 0.5f * VLG_NEGINF ? 1 : 0;
+    for (int k = 0; k < K; ++k) n += C[root + k * stride] > 0.5f * VLG_NEGINF ? 1 : 0;
     return n;
 }
+VLG_HD int kbest_count(const KbCtx& c, int K) { return kbest_count_at(c.C, c.len + 1, c.cells, K); }   // CR(0,len)[k]
 
 }  // namespace vlg

@@ -331,6 +331,19 @@ def dmv1o_log_prob_heads(dec, attach, lengths, heads):
 _KBEST_WS_BYTES = {}
 
 
+def _kbest_frame(name, device, B, N, k, workspace_fn):
+    """What deptree_kbest and dmv1o_kbest share: the outputs heads [k,B,N] / scores [k,B] / count [B] and the workspace of the launch,
+    its size asked of `workspace_fn` (vlg_*_kbest_workspace) once per (name, B, N, k).  Returns (heads, scores, count, ws, nb)."""
+    heads = torch.empty((k, B, N), dtype=torch.int64, device=device)
+    scores = torch.empty((k, B), dtype=torch.float32, device=device)
+    count = torch.empty(B, dtype=torch.int32, device=device)
+    nb = _KBEST_WS_BYTES.get((name, B, N, k))
+    if nb is None:
+        nb = _KBEST_WS_BYTES[(name, B, N, k)] = workspace_fn(B, N, k)
+    ws = torch.empty(nb, dtype=torch.uint8, device=device) if nb else None
+    return heads, scores, count, ws, nb
+
+
 def deptree_kbest(arc, lengths, k):
     """The k best projective single-root trees of arc scores [B,N,N], 1 <= k <= 16, in ONE launch (vlg_deptree_kbest):
     (heads [k,B,N] int64 as deptree_decode writes them, scores [k,B] float32 non-increasing in k, count [B] int32).  A rank at or
@@ -343,14 +356,8 @@ def deptree_kbest(arc, lengths, k):
     k = int(k)
     dt, arc_c = _C.in_dtype(arc)
     lengths = _lengths(lengths, B, arc.device, allow_none=True)
-    heads = torch.empty((k, B, N), dtype=torch.int64, device=arc.device)
-    scores = torch.empty((k, B), dtype=torch.float32, device=arc.device)
-    count = torch.empty(B, dtype=torch.int32, device=arc.device)
     L = _C.lib()
-    nb = _KBEST_WS_BYTES.get((B, N, k))
-    if nb is None:
-        nb = _KBEST_WS_BYTES[(B, N, k)] = L.vlg_deptree_kbest_workspace(B, N, k)
-    ws = torch.empty(nb, dtype=torch.uint8, device=arc.device) if nb else None
+    heads, scores, count, ws, nb = _kbest_frame("deptree_kbest", arc.device, B, N, k, L.vlg_deptree_kbest_workspace)
     _C.check(L.vlg_deptree_kbest(_C.ptr(arc_c), _C.ptr(lengths), B, N, dt, k, _C.ptr(heads), _C.ptr(scores), _C.ptr(count), _C.ptr(ws), nb,
                                  _C.stream_of(arc)), "deptree_kbest")
     return heads, scores, count
@@ -388,9 +395,6 @@ def deptree_kbest_scores(arc, lengths, k):
     return _DepTreeKBestScores.apply(arc, lengths, k)
 
 
-_DMV_KBEST_WS_BYTES = {}
-
-
 def dmv1o_kbest(dec, attach, lengths, k):
     """The k best projective single-root trees of the DMV of root-merged potentials dec [B,N,2,2,2] / attach [B,N,N,2], 1 <= k <= 16,
     in ONE launch (vlg_dmv1o_kbest): (heads [k,B,N] int64 as dmv1o_decode writes them, scores [k,B] float32 non-increasing in k,
@@ -408,14 +412,8 @@ def dmv1o_kbest(dec, attach, lengths, k):
     dt, dec_c = _C.in_dtype(dec)
     _, att_c = _C.in_dtype(attach)
     lengths = _lengths(lengths, B, dec.device)
-    heads = torch.empty((k, B, N), dtype=torch.int64, device=dec.device)
-    scores = torch.empty((k, B), dtype=torch.float32, device=dec.device)
-    count = torch.empty(B, dtype=torch.int32, device=dec.device)
     L = _C.lib()
-    nb = _DMV_KBEST_WS_BYTES.get((B, N, k))
-    if nb is None:
-        nb = _DMV_KBEST_WS_BYTES[(B, N, k)] = L.vlg_dmv1o_kbest_workspace(B, N, k)
-    ws = torch.empty(nb, dtype=torch.uint8, device=dec.device) if nb else None
+    heads, scores, count, ws, nb = _kbest_frame("dmv1o_kbest", dec.device, B, N, k, L.vlg_dmv1o_kbest_workspace)
     _C.check(L.vlg_dmv1o_kbest(_C.ptr(dec_c), _C.ptr(att_c), _C.ptr(lengths), B, N, dt, k, _C.ptr(heads), _C.ptr(scores), _C.ptr(count),
                                _C.ptr(ws), nb, _C.stream_of(dec)), "dmv1o_kbest")
     return heads, scores, count
