@@ -196,7 +196,7 @@ def brute(dec, attach, length, v):
     return logZ, ev, mud, mua, hvd, hva, H, gHd, gHa
 
 
-# ---- the placement plan of vlg_dmv1o_expect, restated (DmvExpectLayout / dmv_expect_plan, vlgae_amd/csrc/vlg_dmv_expect.h) -----------
+# ---- the placement plan of vlg_dmv1o_expect, restated (DmvExpectLayout / dp_plan, vlgae_amd/csrc/vlg_dmv_expect.h) -------------------
 LDS_BUDGET = 160 * 1024
 
 

@@ -152,7 +152,7 @@ def grad_bound(ref64, err32=0.0):
     return max(1e-4 * float(np.abs(ref64).max()), 6.0 * float(err32))
 
 
-# ---- the placement plan of vlg_deptree_expect, restated (ExpectLayout / dp_plan, vlgae_amd/csrc/vlg_dp_core.h) -------------------------
+# ---- the placement plan of vlg_deptree_expect, restated (ExpectLayout / dp_plan, vlgae_amd/csrc/vlg_dp_expect.h) -----------------------
 LDS_BUDGET = 160 * 1024
 
 

@@ -21,7 +21,7 @@ from conftest import ROOT
 HERE = os.path.join(ROOT, "tests", "emu")
 BUILD = os.path.join(HERE, "_build")
 SRC = os.path.join(HERE, "emu_dmv_expect.cpp")
-DEPS = [SRC, os.path.join(HERE, "emu_dp.cpp")] + [os.path.join(ROOT, "vlgae_amd", "csrc", f)
+DEPS = [SRC, os.path.join(HERE, "emu_dp.cpp"), os.path.join(HERE, "emu_expect_common.h")] + [os.path.join(ROOT, "vlgae_amd", "csrc", f)
                                                    for f in ("vlg_dp_core.h", "vlg_dp_expect.h", "vlg_dmv_expect.h")]
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 FIXTURES = ("dmvexpect_B3_N6_s0", "dmvexpect_B4_N12_s1", "dmvexpect_B2_N41_s2")

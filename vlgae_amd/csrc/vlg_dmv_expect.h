@@ -1,7 +1,8 @@
 // vlg_dmv_expect.h -- the DMV1o inside-outside pass in dual numbers (vlg_dmv1o_expect, include/vlgae_amd.h): expected scores, entropy,
 // cross-entropy and KL of DMV1o with their exact gradients (the reference's StructDistribution.entropy / cross_entropy / kl / risk,
 // src/model/torch_struct/distributions.py:79-114, which run the Python width loop of dmv.py:18-69 under EntropySemiring /
-// CrossEntropySemiring / RiskSemiring plus autograd).  The sibling of vlg_dp_expect.h for the valence DMV.
+// CrossEntropySemiring / RiskSemiring plus autograd).  The sibling of vlg_dp_expect.h for the valence DMV: the placement rule, the
+// direction load, the adjoint weight and the lane plan of a width are that header's.
 //
 // Like the phase bodies of vlg_dp_core.h this is the work of ONE thread (tid of nt) between barriers, written against a policy X,
 // and shared by the gfx950 kernel (vlg_dmv_expect.hip) and the host emulator of the CPU test-suite (tests/emu/emu_dmv_expect.cpp).
@@ -45,38 +46,32 @@ struct DmvExpectCtx {
     float *decs, *decsd;       // staged dec [Ne][8] (log2 units) and its tangent
 };
 
-// The dual-number DMV1o pass: every chart of DmvLayout's Log-semiring set next to its tangent chart, plus the staged dec pair.
-//   grad (any of mu / hv wanted), 80 bytes per cell:  0: everything   1: the three adjoint pairs (values, tape and their tangents in
-//     the workspace)   2: gCc, gCi and their tangents   3: staging only -- the adjoint pairs stay in LDS longest, as in ExpectLayout.
-//   forward only, 32 bytes per cell (no tape, no adjoints):  0: everything   1: C, I (their tangents in the workspace)   2, 3: staging only.
-struct DmvExpectLayout {
-    Region C, I, S, Cd, Id, Sd, gCc, gCi, gI, gCcd, gCid, gId, decs, decsd;
-    size_t lds_bytes, ws_bytes;
-    VLG_HOSTDEV_M DmvExpectLayout(int N, bool grad, bool, int mode, bool = false) {
-        const size_t cells = (size_t)N * chart_pitch(N), c4 = grad ? cells * 4 : 0, c8 = grad ? cells * 8 : 0;
-        const bool v = mode < 1, ci = grad ? v : mode < 2, a1 = mode < 3, a2 = mode < 2;   // ci: where C and I go
-        Carver k;
-        C = k.take(cells * 8, ci);
-        I = k.take(cells * 8, ci);
-        S = k.take(c4, v);
-        Cd = k.take(cells * 8, v);
-        Id = k.take(cells * 8, v);
-        Sd = k.take(c4, v);
-        gCc = k.take(c4, a1);
-        gCcd = k.take(c4, a1);
-        gCi = k.take(c8, a1);
-        gCid = k.take(c8, a1);
-        gI = k.take(c8, a2);
-        gId = k.take(c8, a2);
-        decs = k.take((size_t)N * 32, true);
-        decsd = k.take((size_t)N * 32, true);
-        lds_bytes = k.lds;
-        ws_bytes = k.ws;
-    }
-};
+// The placement rule of vlg_dp_expect.h over DMV1o's cells: two valences in a C / I / gCi / gI cell (80 bytes of charts per chart cell
+// with an outside pass, 32 without), and the staged dec pair [N][8] and its direction behind them.
+using DmvExpectLayout = ExpectLayoutOf<8, 32>;
 
-// which kernel image runs and where a sentence's charts live (one body: the launcher takes placement_of(image))
-VLG_HOSTDEV DpPlan dmv_expect_plan(int N, bool grad) { return dp_plan<DmvExpectLayout>(N, grad, false); }
+template <typename At>
+VLG_HD DmvExpectCtx dmv_expect_carve(const DmvExpectLayout& L, int N, int len, const At& at) {
+    DmvExpectCtx c;
+    c.Ne = len + 1;
+    c.len = len;
+    c.P = chart_pitch(N);
+    c.C = (float2*)at(L.C);
+    c.I = (float2*)at(L.I);
+    c.S = (float*)at(L.S);
+    c.Cd = (float2*)at(L.Cd);
+    c.Id = (float2*)at(L.Id);
+    c.Sd = (float*)at(L.Sd);
+    c.gCc = (float*)at(L.gCc);
+    c.gCi = (float2*)at(L.gCi);
+    c.gI = (float2*)at(L.gI);
+    c.gCcd = (float*)at(L.gCcd);
+    c.gCid = (float2*)at(L.gCid);
+    c.gId = (float2*)at(L.gId);
+    c.decs = (float*)at(L.decs);
+    c.decsd = (float*)at(L.decsd);
+    return c;
+}
 
 // "forbidden": at or below the semiring zero DMV1o.merge writes.  bf16 rounds -1e12 to a smaller magnitude, so the test is against
 // half of it; -inf, everything below the clamp floor and NaN (the comparison is false) are covered too.
@@ -217,12 +212,6 @@ VLG_HD void dmv_expect_bw_span(const DmvExpectCtx& c, int w, int G, int D, bool 
     }
 }
 
-// the direction's component at element i of a dec- or attach-shaped pair of tensors (each may be null = 0)
-template <typename VIn>
-VLG_HD float dmv_expect_dir(const typename VIn::T* v, const typename VIn::T* v_sub, size_t i) {
-    return (v ? VIn::ld(v, i) : 0.f) - (v_sub ? VIn::ld(v_sub, i) : 0.f);
-}
-
 struct DmvExpectIO {   // one sentence's tensors; every pointer but dec and attach may be null
     const void *dec, *attach, *v_dec, *v_attach, *v_sub_dec, *v_sub_attach;
     float *logZ, *ev, *mu_dec, *mu_attach, *hv_dec, *hv_attach;
@@ -250,7 +239,7 @@ VLG_HD void dmv_expect_run(const DmvExpectCtx& c, const DmvExpectIO& io, int N, 
     }
     for (int i = tid; i < Ne * 8; i += nt) {
         const float p = In::ld(dec, i);
-        float d = dmv_expect_dir<VIn>(vd, sd, i);
+        float d = expect_dir<VIn>(vd, sd, i);
         if (!dmv_expect_allowed(p)) d = 0.f;   // a forbidden decision carries no tangent, whatever v holds there
         c.decs[i] = pot_clamp(p) * VLG_LOG2E;
         c.decsd[i] = d;
@@ -267,7 +256,7 @@ VLG_HD void dmv_expect_run(const DmvExpectCtx& c, const DmvExpectIO& io, int N, 
         } else {
             const size_t at = ((size_t)h * N + ch) * 2;
             const float2 a = In::ld2(attach, at);
-            float2 t = make_float2(dmv_expect_dir<VIn>(va, sa, at), dmv_expect_dir<VIn>(va, sa, at + 1));
+            float2 t = make_float2(expect_dir<VIn>(va, sa, at), expect_dir<VIn>(va, sa, at + 1));
             if (!dmv_expect_allowed(a.x)) t.x = 0.f;
             if (!dmv_expect_allowed(a.y)) t.y = 0.f;
             const int k = ch < h ? h * P + ch : h * P + ch + 1, go = ch < h ? 0 : 4;   // dec[h,dir,val,GO] at go + 2 val
@@ -281,14 +270,14 @@ VLG_HD void dmv_expect_run(const DmvExpectCtx& c, const DmvExpectIO& io, int N, 
     const bool right = x.uniform(tid >= nd);
     const int t = right ? tid - nd : tid;
     for (int w = 1; w < Ne; ++w) {
-        const int spans = Ne - w, lg = group_log2(spans, w, nd, VLG_DP_LANES_FW), G = 1 << lg;
-        const int per = nd >> lg, rr = t & (G - 1), slot = t >> lg;
-        for (int base = 0; base < spans; base += per) {
-            const bool live = base + slot < spans;
-            if (X::kSkipDeadWaves && (base + ((t & ~63) >> lg)) >= spans) continue;
-            const int D = VLG_MUL24(live ? base + slot : 0, P + 1);
-            if (right) dmv_expect_fw_span<GRAD, 1>(c, w, G, D, live, rr, x);
-            else dmv_expect_fw_span<GRAD, 0>(c, w, G, D, live, rr, x);
+        const int spans = Ne - w;
+        const ExpectLanes l(spans, w, nd, t, VLG_DP_LANES_FW);
+        for (int base = 0; base < spans; base += l.per) {
+            const bool live = base + l.slot < spans;
+            if (X::kSkipDeadWaves && (base + ((t & ~63) >> l.lg)) >= spans) continue;
+            const int D = VLG_MUL24(live ? base + l.slot : 0, P + 1);
+            if (right) dmv_expect_fw_span<GRAD, 1>(c, w, l.G, D, live, l.rr, x);
+            else dmv_expect_fw_span<GRAD, 0>(c, w, l.G, D, live, l.rr, x);
         }
         x.sync();
     }
@@ -301,14 +290,14 @@ VLG_HD void dmv_expect_run(const DmvExpectCtx& c, const DmvExpectIO& io, int N, 
     if (tid == 0) c.gCc[len + 1] = 1.f;   // seed (1, 0)
     x.sync();
     for (int w = Ne - 1; w >= 1; --w) {
-        const int spans = Ne - w, lg = group_log2(spans, w, nd, VLG_DP_LANES_BW), G = 1 << lg;
-        const int per = nd >> lg, rr = t & (G - 1), slot = t >> lg;
-        for (int base = 0; base < spans; base += per) {
-            const bool live = base + slot < spans;
-            if (X::kSkipDeadWaves && (base + ((t & ~63) >> lg)) >= spans) continue;
-            const int D = VLG_MUL24(live ? base + slot : 0, P + 1);
-            if (right) dmv_expect_bw_span<1>(c, w, G, D, live, rr, x);
-            else dmv_expect_bw_span<0>(c, w, G, D, live, rr, x);
+        const int spans = Ne - w;
+        const ExpectLanes l(spans, w, nd, t, VLG_DP_LANES_BW);
+        for (int base = 0; base < spans; base += l.per) {
+            const bool live = base + l.slot < spans;
+            if (X::kSkipDeadWaves && (base + ((t & ~63) >> l.lg)) >= spans) continue;
+            const int D = VLG_MUL24(live ? base + l.slot : 0, P + 1);
+            if (right) dmv_expect_bw_span<1>(c, w, l.G, D, live, l.rr, x);
+            else dmv_expect_bw_span<0>(c, w, l.G, D, live, l.rr, x);
         }
         x.sync();
     }

@@ -7,35 +7,11 @@
 // every chart cell carries its derivative along the direction (v_dec - v_sub_dec, v_attach - v_sub_attach).  One launch returns logZ,
 // ev = <mu, d>, the expected counts mu and hv = (Hessian of logZ) d; entropy, cross-entropy, KL and expected scores and all their
 // gradients are arithmetic on these.  No atomics, one writer per output element, one barrier per span width.  Charts live in LDS
-// where they fit and in the caller's workspace otherwise (DmvExpectLayout, vlg_dmv_expect.h).
-#include "vlg_dp_kernels.h"
+// where they fit and in the caller's workspace otherwise (DmvExpectLayout, vlg_dmv_expect.h).  The launch frame is vlg_expect_kernels.h.
+#include "vlg_expect_kernels.h"
 #include "vlg_dmv_expect.h"
 
 namespace vlg {
-
-template <bool GRAD, int MODE>
-__device__ __forceinline__ DmvExpectCtx carve_dmv_expect(int N, int len, char* smem, char* wsb) {
-    const DmvExpectLayout L(N, GRAD, false, MODE);
-    DmvExpectCtx c;
-    c.Ne = len + 1;
-    c.len = len;
-    c.P = chart_pitch(N);
-    c.C = region_ptr<float2>(L.C, smem, wsb);
-    c.I = region_ptr<float2>(L.I, smem, wsb);
-    c.S = region_ptr<float>(L.S, smem, wsb);
-    c.Cd = region_ptr<float2>(L.Cd, smem, wsb);
-    c.Id = region_ptr<float2>(L.Id, smem, wsb);
-    c.Sd = region_ptr<float>(L.Sd, smem, wsb);
-    c.gCc = region_ptr<float>(L.gCc, smem, wsb);
-    c.gCi = region_ptr<float2>(L.gCi, smem, wsb);
-    c.gI = region_ptr<float2>(L.gI, smem, wsb);
-    c.gCcd = region_ptr<float>(L.gCcd, smem, wsb);
-    c.gCid = region_ptr<float2>(L.gCid, smem, wsb);
-    c.gId = region_ptr<float2>(L.gId, smem, wsb);
-    c.decs = region_ptr<float>(L.decs, smem, wsb);
-    c.decsd = region_ptr<float>(L.decsd, smem, wsb);
-    return c;
-}
 
 struct DmvExpectArgs {
     const void *dec, *attach, *v_dec, *v_attach, *v_sub_dec, *v_sub_attach;
@@ -68,7 +44,9 @@ __global__ __launch_bounds__(kThreads) void dmv1o_expect_kernel(const DmvExpectA
     }
     using T = typename In::T;
     using VT = typename VIn::T;
-    const DmvExpectCtx c = carve_dmv_expect<GRAD, MODE>(N, len, smem, a.ws + (size_t)b * a.ws_stride);
+    char* wsb = a.ws + (size_t)b * a.ws_stride;
+    const DmvExpectLayout L(N, GRAD, false, MODE);
+    const DmvExpectCtx c = dmv_expect_carve(L, N, len, [&](const Region& r) { return region_ptr<char>(r, smem, wsb); });
     DmvExpectIO io;
     io.dec = (const T*)a.dec + dec_off;
     io.attach = (const T*)a.attach + att_off;
@@ -86,33 +64,11 @@ __global__ __launch_bounds__(kThreads) void dmv1o_expect_kernel(const DmvExpectA
     dmv_expect_run<GRAD, In, VIn>(c, io, N, tid, kThreads, x);
 }
 
-template <bool GRAD, int MODE, typename In, typename VIn>
-static int launch_dmv_expect(const DmvExpectArgs& a) {
-    return launch("dmv1o_expect_kernel", dmv1o_expect_kernel<GRAD, MODE, In, VIn>, dim3(a.B), dim3(kThreads), a.lds, a.s, a);
-}
-
-template <bool GRAD, typename In, typename VIn>
-static int launch_dmv_expect_mode(int mode, const DmvExpectArgs& a) {
-    switch (mode) {
-        case 0: return launch_dmv_expect<GRAD, 0, In, VIn>(a);
-        case 1: return launch_dmv_expect<GRAD, 1, In, VIn>(a);
-        case 2: return launch_dmv_expect<GRAD, 2, In, VIn>(a);
-        default:   // (forward only: placements 2 and 3 are the same, staging only)
-            if constexpr (GRAD) return launch_dmv_expect<GRAD, 3, In, VIn>(a);
-            else return launch_dmv_expect<GRAD, 2, In, VIn>(a);
-    }
-}
-
-template <typename In, typename VIn>
-static int launch_dmv_expect_grad(bool grad, int mode, const DmvExpectArgs& a) {
-    return grad ? launch_dmv_expect_mode<true, In, VIn>(mode, a) : launch_dmv_expect_mode<false, In, VIn>(mode, a);
-}
-
 }  // namespace vlg
 
 extern "C" size_t vlg_dmv1o_expect_workspace(int B, int N, int grad) {
     if (B <= 0 || N < 2 || N > 255) return 0;
-    return vlg::dmv_expect_plan(N, grad != 0).ws_stride * (size_t)B;
+    return vlg::expect_workspace_bytes<vlg::DmvExpectLayout>(B, N, grad != 0);
 }
 
 extern "C" int vlg_dmv1o_expect(const void* dec, const void* attach, const void* v_dec, const void* v_attach, const void* v_sub_dec,
@@ -120,18 +76,11 @@ extern "C" int vlg_dmv1o_expect(const void* dec, const void* attach, const void*
                                 float* ev, float* mu_dec, float* mu_attach, float* hv_dec, float* hv_attach, void* ws, size_t ws_bytes,
                                 void* stream) {
     using namespace vlg;
-    if (int e = check_dp_args("dmv1o_expect", B, N, in_dtype, VLG_SR_LOG)) return e;
-    if (v_dtype != VLG_F32 && v_dtype != VLG_BF16) return set_error(VLG_ERR_DTYPE, "dmv1o_expect: v_dtype %d", v_dtype);
-    if (B == 0) return 0;
-    if (!dec || !attach || !lengths || !logZ)
-        return set_error(VLG_ERR_ARG, "dmv1o_expect: null buffer (dec, attach, lengths and logZ are required)");
-    const bool grad = mu_dec || mu_attach || hv_dec || hv_attach;
-    const DpPlan p = dmv_expect_plan(N, grad);
-    if (int e = check_dp_workspace("dmv1o_expect", N, p, B, ws, ws_bytes)) return e;
-    const DmvExpectArgs a{dec, attach, v_dec, v_attach, v_sub_dec, v_sub_attach, lengths, B, N, logZ, ev, mu_dec, mu_attach, hv_dec,
-                          hv_attach, (char*)ws, p.ws_stride, p.lds_bytes, (hipStream_t)stream};
-    const int mode = placement_of(p.image);
-    if (in_dtype == VLG_F32)
-        return v_dtype == VLG_F32 ? launch_dmv_expect_grad<F32In, F32In>(grad, mode, a) : launch_dmv_expect_grad<F32In, BF16In>(grad, mode, a);
-    return v_dtype == VLG_F32 ? launch_dmv_expect_grad<BF16In, F32In>(grad, mode, a) : launch_dmv_expect_grad<BF16In, BF16In>(grad, mode, a);
+    return expect_entry<DmvExpectLayout>("dmv1o_expect", B, N, in_dtype, v_dtype, "dec, attach, lengths and logZ", dec && attach && lengths && logZ,
+                                         mu_dec || mu_attach || hv_dec || hv_attach, ws, ws_bytes,
+                                         [&](const DpPlan& p, auto G, auto M, auto I, auto V) {
+        const DmvExpectArgs a{dec, attach, v_dec, v_attach, v_sub_dec, v_sub_attach, lengths, B, N, logZ, ev, mu_dec, mu_attach, hv_dec,
+                              hv_attach, (char*)ws, p.ws_stride, p.lds_bytes, (hipStream_t)stream};
+        return launch("dmv1o_expect_kernel", dmv1o_expect_kernel<G.value, M.value, decltype(I), decltype(V)>, dim3(B), dim3(kThreads), a.lds, a.s, a);
+    });
 }

@@ -10,6 +10,7 @@
 // Reference behaviour reproduced: src/model/torch_struct/dmv.py:19-66, deptree.py:25-76,
 // helpers.py:101-157 (sum / marginals via autograd), distributions.py:253-265 (merge).
 #include "vlg_dp_kernels.h"
+#include "vlg_dp_expect.h"
 
 #ifdef VLG_DP_HEADLINE_ONLY   // tools/build_variant.sh: a one-file library with only the Log / bf16 DMV1o kernels (compiles in seconds)
 #define VLG_INST_FAMILY 0
@@ -280,8 +281,8 @@ size_t vlg_workspace_bytes(int op, int B, int N, int semiring) {
         case VLG_OP_DMV1O_INSIDE_OUTSIDE: return dp_plan<DmvLayout>(N, true, is_max).ws_stride * B;
         case VLG_OP_DEPTREE_INSIDE: return dp_plan<DepLayout>(N, false, is_max).ws_stride * B;
         case VLG_OP_DEPTREE_INSIDE_OUTSIDE: return dp_plan<DepLayout>(N, true, is_max).ws_stride * B;
-        case VLG_OP_DEPTREE_EXPECT: return is_max ? 0 : dp_plan<ExpectLayout>(N, false, false).ws_stride * B;   // Log semiring only
-        case VLG_OP_DEPTREE_EXPECT_GRAD: return is_max ? 0 : dp_plan<ExpectLayout>(N, true, false).ws_stride * B;
+        case VLG_OP_DEPTREE_EXPECT: return is_max ? 0 : expect_workspace_bytes<ExpectLayout>(B, N, false);   // Log semiring only
+        case VLG_OP_DEPTREE_EXPECT_GRAD: return is_max ? 0 : expect_workspace_bytes<ExpectLayout>(B, N, true);
         default: return 0;
     }
 }

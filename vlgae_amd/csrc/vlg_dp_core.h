@@ -2436,35 +2436,6 @@ struct DepLayout {
     }
 };
 
-// The dual-number DepTree pass (vlg_dp_expect.h): every chart of DepLayout's Log-semiring set next to its tangent chart.
-//   grad (mu and / or hv wanted), twelve charts:  0: everything   1: the three adjoint pairs (values, tape and their tangents in the
-//     workspace)   2: gCc, gCi and their tangents   3: nothing -- the adjoint pairs stay in LDS longest, as in DepLayout.
-//   forward only, four charts (no tape, no adjoints):  0: everything   1: C, I (their tangents in the workspace)   2, 3: nothing.
-// (dp_plan's short-sentence image is the same kernel here: the launcher takes placement_of(image).)
-struct ExpectLayout {
-    Region C, I, S, Cd, Id, Sd, gCc, gCi, gI, gCcd, gCid, gId;
-    size_t lds_bytes, ws_bytes;
-    VLG_HOSTDEV_M ExpectLayout(int N, bool grad, bool, int mode, bool = false) {
-        const size_t cells = (size_t)N * chart_pitch(N), ch = cells * 4, tape = grad ? ch : 0, adj = grad ? ch : 0;
-        const bool v = mode < 1, ci = grad ? v : mode < 2, a1 = mode < 3, a2 = mode < 2;   // ci: where C and I go
-        Carver k;
-        C = k.take(ch, ci);
-        I = k.take(ch, ci);
-        S = k.take(tape, v);
-        Cd = k.take(ch, v);
-        Id = k.take(ch, v);
-        Sd = k.take(tape, v);
-        gCc = k.take(adj, a1);
-        gCcd = k.take(adj, a1);
-        gCi = k.take(adj, a1);
-        gCid = k.take(adj, a1);
-        gI = k.take(adj, a2);
-        gId = k.take(adj, a2);
-        lds_bytes = k.lds;
-        ws_bytes = k.ws;
-    }
-};
-
 template <typename Layout>
 VLG_HOSTDEV int pick_mode(int N, bool bwd, bool is_max, size_t lds_budget, bool walk = false) {
     for (int mode = 0; mode < 3; ++mode)

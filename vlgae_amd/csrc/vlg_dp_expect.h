@@ -5,7 +5,10 @@
 //
 // Like the phase bodies of vlg_dp_core.h this is the work of ONE thread (tid of nt) between barriers, written against a policy X,
 // and shared by the gfx950 kernel (vlg_expect.hip) and the host emulator of the CPU test-suite (tests/emu/emu_expect.cpp).  Nothing
-// here is a CPU fallback.
+// here is a CPU fallback.  What the DMV1o pass (vlg_dmv_expect.h) shares with this one also stands here: the placement rule of the
+// charts (ExpectLayoutOf), the size of a batch's workspace, the direction load (expect_dir), the adjoint weight (expect_adj) and the
+// lane plan of a width (ExpectLanes); the launch frame of both kernels is vlg_expect_kernels.h.  What stayed apart, and why:
+// profiles/expect_frame_neutrality.md.
 //
 // Every chart cell of DepTree (notation: the comment above DepCtx) carries a value and a TANGENT: its derivative along a direction
 // v in potential space.  Values are kept in log2 units as in the family; tangents are in natural units and need no rescaling (their
@@ -32,6 +35,68 @@ struct ExpectCtx {
     float *gCc, *gCi, *gI;     // adjoints, split as in DepCtx
     float *gCcd, *gCid, *gId;  // their tangents
 };
+
+// Where the charts of a dual-number pass live: every chart of the model's Log-semiring set next to its tangent chart.  One placement
+// rule for both models (DmvExpectLayout, vlg_dmv_expect.h); W = bytes of a C / I / gCi / gI cell (S and gCc cells have 4), STAGE =
+// bytes per word of the staged potentials and their direction behind the charts (always in LDS; 0 = none).
+//   grad (mu and / or hv wanted), twelve charts:  0: everything   1: the three adjoint pairs (values, tape and their tangents in the
+//     workspace)   2: gCc, gCi and their tangents   3: staging only -- the adjoint pairs stay in LDS longest, as in DepLayout.
+//   forward only, four charts (no tape, no adjoints):  0: everything   1: C, I (their tangents in the workspace)   2, 3: staging only.
+// (dp_plan's short-sentence image is the same kernel here: the launchers take placement_of(image).)
+template <int W, int STAGE>
+struct ExpectLayoutOf {
+    Region C, I, S, Cd, Id, Sd, gCc, gCi, gI, gCcd, gCid, gId, decs, decsd;
+    size_t lds_bytes, ws_bytes;
+    VLG_HOSTDEV_M ExpectLayoutOf(int N, bool grad, bool, int mode, bool = false) {
+        const size_t cells = (size_t)N * chart_pitch(N), val = cells * W, c4 = grad ? cells * 4 : 0, cw = grad ? val : 0;
+        const bool v = mode < 1, ci = grad ? v : mode < 2, a1 = mode < 3, a2 = mode < 2;   // ci: where C and I go
+        Carver k;
+        C = k.take(val, ci);
+        I = k.take(val, ci);
+        S = k.take(c4, v);
+        Cd = k.take(val, v);
+        Id = k.take(val, v);
+        Sd = k.take(c4, v);
+        gCc = k.take(c4, a1);
+        gCcd = k.take(c4, a1);
+        gCi = k.take(cw, a1);
+        gCid = k.take(cw, a1);
+        gI = k.take(cw, a2);
+        gId = k.take(cw, a2);
+        decs = k.take((size_t)N * STAGE, true);
+        decsd = k.take((size_t)N * STAGE, true);
+        lds_bytes = k.lds;
+        ws_bytes = k.ws;
+    }
+};
+using ExpectLayout = ExpectLayoutOf<4, 0>;
+
+// the workspace of a batch under Layout: what the launchers check and both size queries return
+template <typename Layout>
+VLG_HOSTDEV size_t expect_workspace_bytes(int B, int N, bool grad) { return dp_plan<Layout>(N, grad, false).ws_stride * (size_t)B; }
+
+// One sentence's context over its layout; at(Region) gives the address of a region (the kernel: LDS or the sentence's slice of the
+// workspace; the emulator: its two arenas).
+template <typename At>
+VLG_HD ExpectCtx expect_carve(const ExpectLayout& L, int N, int len, const At& at) {
+    ExpectCtx c;
+    c.Ne = len + 1;
+    c.len = len;
+    c.P = chart_pitch(N);
+    c.C = (float*)at(L.C);
+    c.I = (float*)at(L.I);
+    c.S = (float*)at(L.S);
+    c.Cd = (float*)at(L.Cd);
+    c.Id = (float*)at(L.Id);
+    c.Sd = (float*)at(L.Sd);
+    c.gCc = (float*)at(L.gCc);
+    c.gCi = (float*)at(L.gCi);
+    c.gI = (float*)at(L.gI);
+    c.gCcd = (float*)at(L.gCcd);
+    c.gCid = (float*)at(L.gCid);
+    c.gId = (float*)at(L.gId);
+    return c;
+}
 
 // Inside, one span, one direction: DIR 0 = T -> IL(j,i) -> CL(j,i), DIR 1 = T -> IR(i,j) -> CR(i,j) (see dep_fw_span).
 template <bool GRAD, int DIR, typename X>
@@ -86,6 +151,12 @@ VLG_HD void expect_fw_span(const ExpectCtx& c, int w, int G, int D, bool live, i
     }
 }
 
+// the direction's component at element i of a pair of tensors shaped like a potential (each may be null = 0)
+template <typename VIn>
+VLG_HD float expect_dir(const typename VIn::T* v, const typename VIn::T* v_sub, size_t i) {
+    return (v ? VIn::ld(v, i) : 0.f) - (v_sub ? VIn::ld(v_sub, i) : 0.f);
+}
+
 // weight of a term (value t, tangent td) of a cell (value out, tangent outd) under the adjoint (g, gd): adj_w and its derivative
 VLG_HD void expect_adj(float g, float gd, float t, float td, float out, float outd, float& wv, float& wd) {
     const float p = VLG_EXP(fminf(t - out, 0.f));
@@ -131,6 +202,14 @@ VLG_HD void expect_bw_span(const ExpectCtx& c, int w, int G, int D, int rr) {
     }
 }
 
+// The lane plan of a width on one half of the workgroup (nd lanes, this one is lane t of them; `cap` = VLG_DP_LANES_FW / _BW): groups of
+// G = 1 << lg lanes, `per` groups side by side; this lane is lane rr of group `slot`.
+struct ExpectLanes {
+    int lg, G, per, rr, slot;
+    VLG_HDM ExpectLanes(int spans, int w, int nd, int t, int cap)
+        : lg(group_log2(spans, w, nd, cap)), G(1 << lg), per(nd >> lg), rr(t & (G - 1)), slot(t >> lg) {}
+};
+
 // One sentence: the body of one workgroup.  arc, v, v_sub, mu, hv point at THIS sentence; v, v_sub, ev, mu, hv may be null.
 template <bool GRAD, typename In, typename VIn, typename X>
 VLG_HD void expect_run(const ExpectCtx& c, const typename In::T* arc, const typename VIn::T* v, const typename VIn::T* v_sub, int N,
@@ -155,7 +234,7 @@ VLG_HD void expect_run(const ExpectCtx& c, const typename In::T* arc, const type
         } else {
             const size_t at = (size_t)h * N + ch;
             const float a = pot_clamp(In::ld(arc, at));
-            float d = (v ? VIn::ld(v, at) : 0.f) - (v_sub ? VIn::ld(v_sub, at) : 0.f);
+            float d = expect_dir<VIn>(v, v_sub, at);
             if (!(a > VLG_POT_FLOOR)) d = 0.f;   // a forbidden arc carries no tangent, whatever v holds there
             const int k = ch < h ? h * P + ch : h * P + ch + 1;
             c.I[k] = a * VLG_LOG2E;
@@ -167,14 +246,14 @@ VLG_HD void expect_run(const ExpectCtx& c, const typename In::T* arc, const type
     const bool right = x.uniform(tid >= nd);
     const int t = right ? tid - nd : tid;
     for (int w = 1; w < Ne; ++w) {
-        const int spans = Ne - w, lg = group_log2(spans, w, nd, VLG_DP_LANES_FW), G = 1 << lg;
-        const int per = nd >> lg, rr = t & (G - 1), slot = t >> lg;
-        for (int base = 0; base < spans; base += per) {
-            const bool live = base + slot < spans;
-            if (X::kSkipDeadWaves && (base + ((t & ~63) >> lg)) >= spans) continue;
-            const int D = VLG_MUL24(live ? base + slot : 0, P + 1);
-            if (right) expect_fw_span<GRAD, 1>(c, w, G, D, live, rr, x);
-            else expect_fw_span<GRAD, 0>(c, w, G, D, live, rr, x);
+        const int spans = Ne - w;
+        const ExpectLanes l(spans, w, nd, t, VLG_DP_LANES_FW);
+        for (int base = 0; base < spans; base += l.per) {
+            const bool live = base + l.slot < spans;
+            if (X::kSkipDeadWaves && (base + ((t & ~63) >> l.lg)) >= spans) continue;
+            const int D = VLG_MUL24(live ? base + l.slot : 0, P + 1);
+            if (right) expect_fw_span<GRAD, 1>(c, w, l.G, D, live, l.rr, x);
+            else expect_fw_span<GRAD, 0>(c, w, l.G, D, live, l.rr, x);
         }
         x.sync();
     }
@@ -186,12 +265,12 @@ VLG_HD void expect_run(const ExpectCtx& c, const typename In::T* arc, const type
     if (tid == 0) c.gCc[len + 1] = 1.f;   // seed (1, 0)
     x.sync();
     for (int w = Ne - 1; w >= 1; --w) {
-        const int spans = Ne - w, lg = group_log2(spans, w, nd, VLG_DP_LANES_BW), G = 1 << lg;
-        const int per = nd >> lg, rr = t & (G - 1), slot = t >> lg;
-        for (int base = slot; base < spans; base += per) {
+        const int spans = Ne - w;
+        const ExpectLanes l(spans, w, nd, t, VLG_DP_LANES_BW);
+        for (int base = l.slot; base < spans; base += l.per) {
             const int D = VLG_MUL24(base, P + 1);
-            if (right) expect_bw_span<1>(c, w, G, D, rr);
-            else expect_bw_span<0>(c, w, G, D, rr);
+            if (right) expect_bw_span<1>(c, w, l.G, D, l.rr);
+            else expect_bw_span<0>(c, w, l.G, D, l.rr);
         }
         x.sync();
     }

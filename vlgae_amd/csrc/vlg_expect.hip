@@ -7,33 +7,10 @@
 // every chart cell carries its derivative along the direction v - v_sub.  One launch returns logZ, ev = <mu, v>, the arc marginals
 // mu and hv = (Hessian of logZ) v; entropy, cross-entropy, KL and expected scores and all their gradients are arithmetic on these.
 // No atomics, one writer per output element, one barrier per span width.  Charts live in LDS where they fit and in the caller's
-// workspace otherwise (ExpectLayout, vlg_dp_core.h).
-#include "vlg_dp_kernels.h"
-#include "vlg_dp_expect.h"
+// workspace otherwise (ExpectLayout, vlg_dp_expect.h).  The launch frame is vlg_expect_kernels.h.
+#include "vlg_expect_kernels.h"
 
 namespace vlg {
-
-template <bool GRAD, int MODE>
-__device__ __forceinline__ ExpectCtx carve_expect(int N, int len, char* smem, char* wsb) {
-    const ExpectLayout L(N, GRAD, false, MODE);
-    ExpectCtx c;
-    c.Ne = len + 1;
-    c.len = len;
-    c.P = chart_pitch(N);
-    c.C = region_ptr<float>(L.C, smem, wsb);
-    c.I = region_ptr<float>(L.I, smem, wsb);
-    c.S = region_ptr<float>(L.S, smem, wsb);
-    c.Cd = region_ptr<float>(L.Cd, smem, wsb);
-    c.Id = region_ptr<float>(L.Id, smem, wsb);
-    c.Sd = region_ptr<float>(L.Sd, smem, wsb);
-    c.gCc = region_ptr<float>(L.gCc, smem, wsb);
-    c.gCi = region_ptr<float>(L.gCi, smem, wsb);
-    c.gI = region_ptr<float>(L.gI, smem, wsb);
-    c.gCcd = region_ptr<float>(L.gCcd, smem, wsb);
-    c.gCid = region_ptr<float>(L.gCid, smem, wsb);
-    c.gId = region_ptr<float>(L.gId, smem, wsb);
-    return c;
-}
 
 template <bool GRAD, int MODE, typename In, typename VIn>
 __global__ __launch_bounds__(kThreads) void deptree_expect_kernel(const typename In::T* __restrict__ arc, const typename VIn::T* __restrict__ v,
@@ -55,44 +32,12 @@ __global__ __launch_bounds__(kThreads) void deptree_expect_kernel(const typename
         }
         return;
     }
-    const ExpectCtx c = carve_expect<GRAD, MODE>(N, len, smem, ws + (size_t)b * ws_stride);
+    char* wsb = ws + (size_t)b * ws_stride;
+    const ExpectLayout L(N, GRAD, false, MODE);
+    const ExpectCtx c = expect_carve(L, N, len, [&](const Region& r) { return region_ptr<char>(r, smem, wsb); });
     DevX x;
     expect_run<GRAD, In, VIn>(c, arc + off, v ? v + off : nullptr, v_sub ? v_sub + off : nullptr, N, logZ + b, ev ? ev + b : nullptr,
                               (GRAD && mu) ? mu + off : nullptr, (GRAD && hv) ? hv + off : nullptr, tid, kThreads, x);
-}
-
-struct ExpectArgs {
-    const void *arc, *v, *v_sub;
-    const int64_t* lengths;
-    int B, N;
-    float *logZ, *ev, *mu, *hv;
-    void* ws;
-    size_t ws_stride, lds;
-    hipStream_t s;
-};
-
-template <bool GRAD, int MODE, typename In, typename VIn>
-static int launch_expect(const ExpectArgs& a) {
-    return launch("deptree_expect_kernel", deptree_expect_kernel<GRAD, MODE, In, VIn>, dim3(a.B), dim3(kThreads), a.lds, a.s,
-                  (const typename In::T*)a.arc, (const typename VIn::T*)a.v, (const typename VIn::T*)a.v_sub, a.lengths, a.N, a.logZ, a.ev, a.mu,
-                  a.hv, (char*)a.ws, a.ws_stride);
-}
-
-template <bool GRAD, typename In, typename VIn>
-static int launch_expect_mode(int mode, const ExpectArgs& a) {
-    switch (mode) {
-        case 0: return launch_expect<GRAD, 0, In, VIn>(a);
-        case 1: return launch_expect<GRAD, 1, In, VIn>(a);
-        case 2: return launch_expect<GRAD, 2, In, VIn>(a);
-        default:   // (forward only: placements 2 and 3 are the same, everything in the workspace)
-            if constexpr (GRAD) return launch_expect<GRAD, 3, In, VIn>(a);
-            else return launch_expect<GRAD, 2, In, VIn>(a);
-    }
-}
-
-template <typename In, typename VIn>
-static int launch_expect_grad(bool grad, int mode, const ExpectArgs& a) {
-    return grad ? launch_expect_mode<true, In, VIn>(mode, a) : launch_expect_mode<false, In, VIn>(mode, a);
 }
 
 }  // namespace vlg
@@ -100,16 +45,12 @@ static int launch_expect_grad(bool grad, int mode, const ExpectArgs& a) {
 extern "C" int vlg_deptree_expect(const void* arc, const void* v, const void* v_sub, const int64_t* lengths, int B, int N, int in_dtype,
                                   int v_dtype, float* logZ, float* ev, float* mu, float* hv, void* ws, size_t ws_bytes, void* stream) {
     using namespace vlg;
-    if (int e = check_dp_args("deptree_expect", B, N, in_dtype, VLG_SR_LOG)) return e;
-    if (v_dtype != VLG_F32 && v_dtype != VLG_BF16) return set_error(VLG_ERR_DTYPE, "deptree_expect: v_dtype %d", v_dtype);
-    if (B == 0) return 0;
-    if (!arc || !logZ) return set_error(VLG_ERR_ARG, "deptree_expect: null buffer (arc and logZ are required)");
-    const bool grad = mu || hv;
-    const DpPlan p = dp_plan<ExpectLayout>(N, grad, false);
-    if (int e = check_dp_workspace("deptree_expect", N, p, B, ws, ws_bytes)) return e;
-    const ExpectArgs a{arc, v, v_sub, lengths, B, N, logZ, ev, mu, hv, ws, p.ws_stride, p.lds_bytes, (hipStream_t)stream};
-    const int mode = placement_of(p.image);
-    if (in_dtype == VLG_F32)
-        return v_dtype == VLG_F32 ? launch_expect_grad<F32In, F32In>(grad, mode, a) : launch_expect_grad<F32In, BF16In>(grad, mode, a);
-    return v_dtype == VLG_F32 ? launch_expect_grad<BF16In, F32In>(grad, mode, a) : launch_expect_grad<BF16In, BF16In>(grad, mode, a);
+    return expect_entry<ExpectLayout>("deptree_expect", B, N, in_dtype, v_dtype, "arc and logZ", arc && logZ, mu || hv, ws, ws_bytes,
+                                      [&](const DpPlan& p, auto G, auto M, auto I, auto V) {
+        using In = decltype(I);
+        using VIn = decltype(V);
+        return launch("deptree_expect_kernel", deptree_expect_kernel<G.value, M.value, In, VIn>, dim3(B), dim3(kThreads), p.lds_bytes,
+                      (hipStream_t)stream, (const typename In::T*)arc, (const typename VIn::T*)v, (const typename VIn::T*)v_sub, lengths, N, logZ, ev,
+                      mu, hv, (char*)ws, p.ws_stride);
+    });
 }

@@ -658,6 +658,32 @@ def deptree_sum(arc, lengths, semiring):
     return _DepTreeSum.apply(arc, lengths, semiring)
 
 
+def _expect_frame(name, device, B, N, *, dirs, shapes, shape_error, grad, outs, ws_bytes):
+    """What deptree_expect and dmv1o_expect share.  Each given direction of `dirs` is on the GPU and has the shape of its potential
+    (`shapes`, in step; `shape_error` opens the message); they go in one storage type -- bf16 only when every one given is bf16, else
+    detached float32 -- and contiguous.  logZ [B], ev [B] and the outputs of the shapes `outs` (None: not wanted) are float32 in one
+    allocation; the workspace has ws_bytes(B, N, grad) bytes, asked once per (name, B, N, grad).
+    Returns (dirs, v_dtype, (logZ, ev, *outputs), ws, nb)."""
+    for t, want in zip(dirs, shapes):
+        if t is not None:
+            _C.require_gpu(t, name)
+            if tuple(t.shape) != want:
+                raise ValueError(f"{shape_error}, got {tuple(t.shape)}")
+    vdt = _C.F32
+    given = [t for t in dirs if t is not None]
+    if given:
+        if all(t.dtype == torch.bfloat16 for t in given):
+            vdt = _C.BF16
+        else:
+            dirs = [None if t is None else t.detach().float() for t in dirs]
+        dirs = [None if t is None else (t if t.is_contiguous() else t.contiguous()) for t in dirs]
+    out, _ = _C.alloc_f32(device, [(B,), (B,), *outs])
+    nb = _WS_BYTES.get((name, B, N, grad))
+    if nb is None:
+        nb = _WS_BYTES[(name, B, N, grad)] = ws_bytes(B, N, grad)
+    return dirs, vdt, out, torch.empty(nb, dtype=torch.uint8, device=device) if nb else None, nb
+
+
 def deptree_expect(arc, lengths, v=None, v_sub=None, want_mu=False, want_hv=False):
     """Raw launcher of the dual-number DepTree pass (vlg_deptree_expect).  arc [B,N,N]; v, v_sub [B,N,N] or None (= 0): the direction is
     v - v_sub.  Returns (logZ [B], ev [B] = <mu, v - v_sub>, mu [B,N,N] or None, hv [B,N,N] = (Hessian of logZ)(v - v_sub) or None),
@@ -668,24 +694,14 @@ def deptree_expect(arc, lengths, v=None, v_sub=None, want_mu=False, want_hv=Fals
     B, N, N2 = arc.shape
     assert N == N2, "Non-square potentials"
     dt, arc_c = _C.in_dtype(arc)
-    vs = [t for t in (v, v_sub) if t is not None]
-    for t in vs:
-        _C.require_gpu(t, "deptree_expect")
-        if tuple(t.shape) != (B, N, N):
-            raise ValueError(f"direction must be [B,N,N] = {(B, N, N)}, got {tuple(t.shape)}")
-    vdt = _C.F32
-    if vs:   # both directions in one storage type: bf16 only when every one given is bf16
-        if all(t.dtype == torch.bfloat16 for t in vs):
-            vdt = _C.BF16
-        else:
-            v, v_sub = (None if t is None else t.detach().float() for t in (v, v_sub))
-        v, v_sub = (None if t is None else (t if t.is_contiguous() else t.contiguous()) for t in (v, v_sub))
+    shape, L = (B, N, N), _C.lib()
+    (v, v_sub), vdt, (logZ, ev, mu, hv), ws, nb = _expect_frame(
+        "deptree_expect", arc.device, B, N, dirs=(v, v_sub), shapes=(shape, shape), shape_error=f"direction must be [B,N,N] = {shape}",
+        grad=want_mu or want_hv, outs=(shape if want_mu else None, shape if want_hv else None),
+        ws_bytes=lambda B, N, grad: L.vlg_workspace_bytes(_C.OP_DEPTREE_EXPECT_GRAD if grad else _C.OP_DEPTREE_EXPECT, B, N, _C.SEMIRING_LOG))
     lengths = _lengths(lengths, B, arc.device, allow_none=True)
-    grad = want_mu or want_hv
-    (logZ, ev, mu, hv), _ = _C.alloc_f32(arc.device, [(B,), (B,), (B, N, N) if want_mu else None, (B, N, N) if want_hv else None])
-    ws, nb = _workspace(_C.OP_DEPTREE_EXPECT_GRAD if grad else _C.OP_DEPTREE_EXPECT, B, N, _C.SEMIRING_LOG, arc.device)
-    _C.check(_C.lib().vlg_deptree_expect(_C.ptr(arc_c), _C.ptr(v), _C.ptr(v_sub), _C.ptr(lengths), B, N, dt, vdt, _C.ptr(logZ), _C.ptr(ev),
-                                         _C.ptr(mu), _C.ptr(hv), _C.ptr(ws), nb, _C.stream_of(arc)), "deptree_expect")
+    _C.check(L.vlg_deptree_expect(_C.ptr(arc_c), _C.ptr(v), _C.ptr(v_sub), _C.ptr(lengths), B, N, dt, vdt, _C.ptr(logZ), _C.ptr(ev), _C.ptr(mu),
+                                  _C.ptr(hv), _C.ptr(ws), nb, _C.stream_of(arc)), "deptree_expect")
     return logZ, ev, mu, hv
 
 
@@ -1082,31 +1098,14 @@ def dmv1o_expect(dec, attach, lengths, v=None, v_sub=None, want_mu=False, want_h
     dt, dec_c = _C.in_dtype(dec)
     _, att_c = _C.in_dtype(attach)
     dirs = [*(v if v is not None else (None, None)), *(v_sub if v_sub is not None else (None, None))]   # v_dec, v_att, sub_dec, sub_att
-    given = [t for t in dirs if t is not None]
-    for k, t in enumerate(dirs):
-        if t is not None:
-            _C.require_gpu(t, "dmv1o_expect")
-            want = (B, N, 2, 2, 2) if k % 2 == 0 else (B, N, N, 2)
-            if tuple(t.shape) != want:
-                raise ValueError(f"direction must be (dec-shaped, attach-shaped) = ({(B, N, 2, 2, 2)}, {(B, N, N, 2)}), got {tuple(t.shape)}")
-    vdt = _C.F32
-    if given:   # the four directions in one storage type: bf16 only when every one given is bf16
-        if all(t.dtype == torch.bfloat16 for t in given):
-            vdt = _C.BF16
-        else:
-            dirs = [None if t is None else t.detach().float() for t in dirs]
-        dirs = [None if t is None else (t if t.is_contiguous() else t.contiguous()) for t in dirs]
-    lengths = _lengths(lengths, B, dec.device)
-    grad = want_mu or want_hv
     dshape, ashape = (B, N, 2, 2, 2), (B, N, N, 2)
-    (logZ, ev, mu_d, mu_a, hv_d, hv_a), _ = _C.alloc_f32(dec.device, [(B,), (B,), dshape if want_mu else None, ashape if want_mu else None,
-                                                                      dshape if want_hv else None, ashape if want_hv else None])
     L = _C.lib()
-    key = ("dmv1o_expect", B, N, grad)
-    nb = _WS_BYTES.get(key)
-    if nb is None:
-        nb = _WS_BYTES[key] = L.vlg_dmv1o_expect_workspace(B, N, int(grad))
-    ws = torch.empty(nb, dtype=torch.uint8, device=dec.device) if nb else None
+    dirs, vdt, (logZ, ev, mu_d, mu_a, hv_d, hv_a), ws, nb = _expect_frame(
+        "dmv1o_expect", dec.device, B, N, dirs=dirs, shapes=(dshape, ashape) * 2,
+        shape_error=f"direction must be (dec-shaped, attach-shaped) = ({dshape}, {ashape})", grad=want_mu or want_hv,
+        outs=(dshape if want_mu else None, ashape if want_mu else None, dshape if want_hv else None, ashape if want_hv else None),
+        ws_bytes=lambda B, N, grad: L.vlg_dmv1o_expect_workspace(B, N, int(grad)))
+    lengths = _lengths(lengths, B, dec.device)
     _C.check(L.vlg_dmv1o_expect(_C.ptr(dec_c), _C.ptr(att_c), _C.ptr(dirs[0]), _C.ptr(dirs[1]), _C.ptr(dirs[2]), _C.ptr(dirs[3]), _C.ptr(lengths),
                                 B, N, dt, vdt, _C.ptr(logZ), _C.ptr(ev), _C.ptr(mu_d), _C.ptr(mu_a), _C.ptr(hv_d), _C.ptr(hv_a), _C.ptr(ws), nb,
                                 _C.stream_of(dec)), "dmv1o_expect")
